@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — read -> corrected gene-mer graph hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3-sweep|cfg3|cfg2|cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3-sweep|cfg3|cfg2|cfg4] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic gene calls whose CSR
 token arrays (and gene positions) are already resident in HBM:
@@ -86,6 +86,60 @@ def make_tokens(w, lo, hi):
     toks = np.where(sts == 1, vocab.V + r, vocab.V - 1 - r).astype(np.int32)
     offs = (np.arange(hi - lo + 1, dtype=np.int64) * w["L"])
     return vocab, toks.reshape(-1), offs
+
+
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
+
+
+def _exact_float(a):
+    """float32 when every value of the integer array a is exact in it, float64 otherwise"""
+    if a.size == 0 or max(abs(int(a.min())), abs(int(a.max()))) <= 1 << 24:
+        return np.float32
+    return np.float64
+
+
+def dump_outputs(eng, out_dir, seed, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the engine hands its caller after a step — the final graph's nodes and edges, and the node
+    and direction of every window of the final read set — as DIR/<name>.npy, float32 (float64 where a value would not
+    be exact in float32), `budget` bytes in all.  Groups of rows (node, edge, window) share the budget, the smallest
+    first: a group that does not fit its share is cut to a seeded sample of its rows, and <group>_rows.npy holds the
+    indices of the rows kept.  sizes.npy: reads, genes, nodes, directed edges and k of the engine."""
+    n_reads, n_tokens = eng.sizes()
+    n_nodes, n_edges, k = eng.graph_sizes()
+    nodes, edges = eng.nodes(), eng.edges()
+    tok_node, tok_dir = eng.read_nodes()
+    groups = {
+        "node": {"node_" + c: nodes[c] for c in ("tokens", "coverage", "first_token", "first_dir", "component", "alive")},
+        "edge": {"edge_" + c: edges[c] for c in ("src", "tgt", "sdir", "tdir", "coverage", "alive")},
+        "window": {"window_node": tok_node, "window_dir": tok_dir},
+    }
+    dtypes = {name: _exact_float(a) for g in groups.values() for name, a in g.items()}
+    row_bytes = {g: sum(np.dtype(dtypes[n]).itemsize * int(np.prod(a.shape[1:])) for n, a in arrs.items())
+                 for g, arrs in groups.items()}
+    n_rows = {g: len(next(iter(arrs.values()))) for g, arrs in groups.items()}
+    left = budget - 256 * (sum(len(a) for a in groups.values()) + len(groups) + 1)   # (.npy headers)
+    left -= 5 * 8   # sizes.npy
+    files = {"sizes": np.array([n_reads, n_tokens, n_nodes, n_edges, k], np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    order = sorted(groups, key=lambda g: n_rows[g] * row_bytes[g])
+    for i, g in enumerate(order):
+        share = left // (len(order) - i)
+        rows_path = os.path.join(out_dir, g + "_rows.npy")
+        if n_rows[g] * row_bytes[g] <= share:
+            rows = slice(None)
+            left -= n_rows[g] * row_bytes[g]
+            if os.path.exists(rows_path):   # (from an earlier dump into the same directory)
+                os.remove(rows_path)
+        else:   # + 8: the float64 row index beside the sample
+            n = min(share // (row_bytes[g] + 8), n_rows[g])
+            rows = np.sort(np.random.default_rng(seed).choice(n_rows[g], n, replace=False))
+            files[g + "_rows"] = rows.astype(np.float64)
+            left -= n * (row_bytes[g] + 8)
+        for name, a in groups[g].items():
+            files[name] = a[rows].astype(dtypes[name])
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return files
 
 
 # ---------------------------------------------------------------------------------------------
@@ -891,11 +945,18 @@ def main():
                          "reference spells it")
     ap.add_argument("--force-merge", action="store_true",
                     help="run the merged (multi-GPU) code path even at world size 1 (self-test)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0: the final graph and the node "
+                         "of every window) as DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
     w = WORKLOADS[args.workload]
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload == "cfg4":
+        sys.exit("bench.py: --dump-outputs covers the engine's graph workloads (cfg2, cfg3, cfg3-sweep), not cfg4")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     rank = int(os.environ.get("RANK", "0"))
@@ -1057,6 +1118,10 @@ def main():
         t = torch.tensor([dt], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(eng, args.dump_outputs, w["seed"])
+        print(f"bench.py: {len(dumped)} arrays of the last timed step, {sum(a.nbytes for a in dumped.values())} bytes, "
+              f"in {args.dump_outputs}", file=sys.stderr, flush=True)
 
     # ---- the same sweep with its first two steps as one device pass (amg_build_filtered): reported beside `value`
     fused_line = None

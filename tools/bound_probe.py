@@ -1,7 +1,7 @@
 """the node table of every build of the cfg 3 sweep: slots and retries (the rebuilds' tables are sized by the bound the
 correction hands on, amg_correct_reads / amg_adopt_corrected)"""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
 from amira_amd import Engine
 w = bench.WORKLOADS["cfg3-sweep"]; N = 1_000_000; L, k = w["L"], w["k"]
