@@ -64,31 +64,7 @@ extern "C" int amg_set_timing(amg_ctx* c, int on) {
 }
 
 // ------------------------------------------------------------------ clear_many
-struct ClearArgs {
-  void* p[8];
-  unsigned long long words[8];  // 4-byte words per range
-  unsigned int fill[8];         // the word each range is filled with
-  int n;
-};
-__global__ __launch_bounds__(256) void k_clear_many(ClearArgs a) {
-  const unsigned long long stride = (unsigned long long)gridDim.x * 256ull;
-  for (int r = 0; r < a.n; ++r) {
-    unsigned int* p = reinterpret_cast<unsigned int*>(a.p[r]);
-    const unsigned long long w = a.words[r];
-    const unsigned int f = a.fill[r];
-    // 16-byte stores over the aligned middle, words at the ragged ends
-    const unsigned long long head = ((16u - ((unsigned long long)(uintptr_t)p & 15u)) & 15u) >> 2;
-    const unsigned long long h = head < w ? head : w;
-    const unsigned long long quads = (w - h) >> 2;
-    uint4* q = reinterpret_cast<uint4*>(p + h);
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < quads; i += stride)
-      q[i] = make_uint4(f, f, f, f);
-    if (blockIdx.x == 0) {
-      for (unsigned long long i = threadIdx.x; i < h; i += 256) p[i] = f;
-      for (unsigned long long i = h + quads * 4 + threadIdx.x; i < w; i += 256) p[i] = f;
-    }
-  }
-}
+__global__ __launch_bounds__(256) void k_clear_many(ClearArgs a) { clear_args_part(a, blockIdx.x, gridDim.x); }
 
 // The mailbox: FETCH_MAX + 1 slots of {value, ticket} in pinned host memory; the host waits until every slot it asked
 // for carries the ticket of this read-back: value, system-scope fence, ticket with release semantics.  (Value and
@@ -158,15 +134,9 @@ int fetch_status(amg_ctx* c, unsigned long long* out, const ClearList* filler) {
 int clear_many(amg_ctx* c, const ClearList& l) {
   if (l.overflow) return amg_fail(AMG_E_ARG, "clear_many: more than %d ranges in one list", CLEAR_MAX);
   if (l.n == 0) return AMG_OK;
-  ClearArgs a;
+  const ClearArgs a = clear_args(l);
   unsigned long long most = 0;
-  a.n = l.n;
-  for (int i = 0; i < l.n; ++i) {
-    a.p[i] = l.p[i];
-    a.words[i] = l.bytes[i] >> 2;
-    a.fill[i] = l.fill[i];
-    most = a.words[i] > most ? a.words[i] : most;
-  }
+  for (int i = 0; i < a.n; ++i) most = a.words[i] > most ? a.words[i] : most;
   unsigned long long blocks = (most / 4 + 256 * 8 - 1) / (256 * 8);  // ~8 quads per thread at the largest range
   if (blocks < 1) blocks = 1;
   if (blocks > 4096) blocks = 4096;

@@ -14,7 +14,7 @@
 //                     and upsert of one record per adjacency into the edge-class table
 //                     (create_edges / add_edge_to_edges, :246-277; Edge.__hash__ classes,
 //                     construct_edge.py:104-124)
-//   k_compact_slots + sort + k_pair_width + scan + k_emit_edges
+//   k_compact_slots + sort + the pair-width scan that emits the edges (amg_scan.hip)
 //                     directed edges in _edges insertion order, E1 then E2 (:279-285)
 //   k_adj_keys + stable radix sort + k_row_offsets
 //                     forwardEdgeHashes / backwardEdgeHashes lists (:287-298)
@@ -229,34 +229,6 @@ __global__ void k_gather_pairs(const unsigned int* __restrict__ slot_sorted, lon
   const Slot* s = edge_tab + slot_sorted[i];
   pkey[i] = s->key;
   pcnt[i] = s->count;
-}
-
-__global__ void k_emit_edges(const unsigned long long* __restrict__ pkey,
-                             const unsigned int* __restrict__ pcnt,
-                             const unsigned long long* __restrict__ pfirst, long long n_pairs,
-                             const long long* __restrict__ base, int* __restrict__ e_src,
-                             int* __restrict__ e_tgt, signed char* __restrict__ e_sdir,
-                             signed char* __restrict__ e_tdir, unsigned int* __restrict__ e_cov,
-                             unsigned char* __restrict__ e_alive) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_pairs) return;
-  unsigned long long key = pkey[i], first = pfirst[i];
-  int lo = (int)((key >> 32) & 0x7fffffffull);
-  int hi = (int)((key & 0xffffffffull) - 1ull);
-  int X = (first & 1ull) ? lo : hi, Y = (first & 1ull) ? hi : lo;
-  signed char dX = (first & 2ull) ? 1 : -1, dY = (first & 4ull) ? 1 : -1;
-  long long e = base[i];
-  unsigned int cnt = pcnt[i];
-  if (lo == hi) {
-    // E1 and E2 fall in the same class: one edge, +2 per traversal
-    e_src[e] = X; e_tgt[e] = Y; e_sdir[e] = dX; e_tdir[e] = dY;
-    e_cov[e] = cnt * 2u; e_alive[e] = 1;
-  } else {
-    e_src[e] = X; e_tgt[e] = Y; e_sdir[e] = dX; e_tdir[e] = dY;
-    e_cov[e] = cnt; e_alive[e] = 1;
-    e_src[e + 1] = Y; e_tgt[e + 1] = X; e_sdir[e + 1] = (signed char)-dY;
-    e_tdir[e + 1] = (signed char)-dX; e_cov[e + 1] = cnt; e_alive[e + 1] = 1;
-  }
 }
 
 // adjacency rows: row = 2 * src + (sdir == +1 ? 0 : 1); edge ids ascending inside a row
@@ -926,7 +898,6 @@ int bs_pairs_from_local(amg_ctx* c) {
 // graphs of a cleaning sweep only the second needs its components (tip clipping) and none needs the
 // lists of removed edges — the correction walks the LIVE adjacency, built from the live edges alone.
 int bs_finish_from_pairs(amg_ctx* c) {
-  hipStream_t st = c->stream;
   const long long P = c->n_pairs, R = c->n_reads;
   stage_begin(c, "edge_emit");
   AMGCHK(c->s5.ensure((size_t)(P + 2) * sizeof(long long)));
@@ -940,21 +911,20 @@ int bs_finish_from_pairs(amg_ctx* c) {
   AMGCHK(c->edge_cov.ensure((size_t)(cap + 2) * sizeof(unsigned int)));
   AMGCHK(c->edge_alive.ensure((size_t)(cap + 2)));
   AMGCHK(c->read_fix.ensure((size_t)R + 1));
-  {
-    ClearList cl;
-    cl.add(c->read_fix.p, (size_t)R + 1);
-    AMGCHK(clear_many(c, cl));
-  }
   long long total = 0;
-  if (P > 0) {
-    // a class is one directed edge (self-loop) or two: the widths are made by the scan that sums them
-    AMGCHK(prim_exscan_pair_width(c, c->pair_key.as<unsigned long long>(), base, (size_t)P));
-    hipLaunchKernelGGL(k_emit_edges, dim3(blocks_for(P, 256)), dim3(256), 0, st,
-                       c->pair_key.as<unsigned long long>(), c->pair_cnt.as<unsigned int>(),
-                       c->pair_first.as<unsigned long long>(), P, base, c->edge_src.as<int>(),
-                       c->edge_tgt.as<int>(), c->edge_sdir.as<signed char>(),
-                       c->edge_tdir.as<signed char>(), c->edge_cov.as<unsigned int>(),
-                       c->edge_alive.as<unsigned char>());
+  {
+    ClearList cl;  // (zeroed by the scan's workgroups)
+    cl.add(c->read_fix.p, (size_t)R + 1);
+    if (P > 0) {
+      // a class is one directed edge (self-loop) or two: the scan that sums the widths writes the edges at their
+      // places (base[P] = the number of directed edges)
+      AMGCHK(prim_exscan_emit_edges(c, c->pair_key.as<unsigned long long>(), c->pair_cnt.as<unsigned int>(),
+                                    c->pair_first.as<unsigned long long>(), (size_t)P, base + P, c->edge_src.as<int>(),
+                                    c->edge_tgt.as<int>(), c->edge_sdir.as<signed char>(), c->edge_tdir.as<signed char>(),
+                                    c->edge_cov.as<unsigned int>(), c->edge_alive.as<unsigned char>(), &cl));
+    } else {
+      AMGCHK(clear_many(c, cl));
+    }
   }
   {  // the build's final synchronisation; the done flags of its counting sweeps ride along
     FetchList l;

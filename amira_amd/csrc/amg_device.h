@@ -215,6 +215,43 @@ __device__ __forceinline__ void huge_row_in_order(const unsigned int* __restrict
   __syncthreads();
 }
 
+// ------------------------------------------------------------------ range clears (k_clear_many; the scans' side clears)
+struct ClearArgs {
+  void* p[CLEAR_MAX];
+  unsigned long long words[CLEAR_MAX];  // 4-byte words per range
+  unsigned int fill[CLEAR_MAX];         // the word each range is filled with
+  int n;
+};
+static inline ClearArgs clear_args(const ClearList& l) {
+  ClearArgs a;
+  a.n = l.n;
+  for (int i = 0; i < l.n; ++i) {
+    a.p[i] = l.p[i];
+    a.words[i] = l.bytes[i] >> 2;
+    a.fill[i] = l.fill[i];
+  }
+  return a;
+}
+// workgroup `part` of `parts` fills its grid-stride share of every range
+__device__ __forceinline__ void clear_args_part(const ClearArgs& a, unsigned long long part, unsigned long long parts) {
+  const unsigned long long bd = blockDim.x, stride = parts * bd;
+  for (int r = 0; r < a.n; ++r) {
+    unsigned int* p = reinterpret_cast<unsigned int*>(a.p[r]);
+    const unsigned long long w = a.words[r];
+    const unsigned int f = a.fill[r];
+    // 16-byte stores over the aligned middle, words at the ragged ends
+    const unsigned long long head = ((16u - ((unsigned long long)(uintptr_t)p & 15u)) & 15u) >> 2;
+    const unsigned long long h = head < w ? head : w;
+    const unsigned long long quads = (w - h) >> 2;
+    uint4* q = reinterpret_cast<uint4*>(p + h);
+    for (unsigned long long i = part * bd + threadIdx.x; i < quads; i += stride) q[i] = make_uint4(f, f, f, f);
+    if (part == 0) {
+      for (unsigned long long i = threadIdx.x; i < h; i += bd) p[i] = f;
+      for (unsigned long long i = h + quads * 4 + threadIdx.x; i < w; i += bd) p[i] = f;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ union-find helpers (components)
 __device__ __forceinline__ int uf_ld(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // plain load, never hoisted

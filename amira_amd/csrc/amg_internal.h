@@ -296,18 +296,23 @@ int prim_sort_u64_u32(amg_ctx* c, const unsigned long long* kin, unsigned long l
                       const unsigned int* vin, unsigned int* vout, size_t n, int end_bit);
 int prim_sort_u32_u32(amg_ctx* c, const unsigned int* kin, unsigned int* kout,
                       const unsigned int* vin, unsigned int* vout, size_t n, int end_bit);
+struct ClearList;
 int prim_exscan_i64(amg_ctx* c, const long long* in, long long* out, size_t n);
 int prim_exscan_u32_to_i64(amg_ctx* c, const unsigned int* in, long long* out, size_t n);
 int prim_exscan_u32_pair(amg_ctx* c, const unsigned int* in_a, long long* out_a, const unsigned int* in_b, long long* out_b,
                          size_t n);
 int prim_exscan_i64_pair(amg_ctx* c, const long long* in_a, long long* out_a, const long long* in_b, long long* out_b,
                          size_t n);
-int prim_exscan_bytes_set(amg_ctx* c, const unsigned char* in, long long* out, size_t n);
+int prim_exscan_bytes_set(amg_ctx* c, const unsigned char* in, long long* out, size_t n, const ClearList* side = nullptr);
 int prim_exscan_apply_kill(amg_ctx* c, unsigned char* kill, unsigned char* alive, long long* out, size_t n);
 int prim_exscan_keep_and_len(amg_ctx* c, const unsigned int* len, long long* out_keep, long long* out_off, size_t n);
 int prim_exscan_flag_words(amg_ctx* c, const unsigned char* flags, unsigned int* bits, long long* out, size_t n_words);
 int prim_exscan_bits_popc(amg_ctx* c, const unsigned int* bits, long long* out, size_t n_words);
 int prim_exscan_pair_width(amg_ctx* c, const unsigned long long* pkey, long long* out, size_t n_pairs);
+int prim_exscan_emit_edges(amg_ctx* c, const unsigned long long* pkey, const unsigned int* pcnt,
+                           const unsigned long long* pfirst, size_t n_pairs, long long* total, int* e_src, int* e_tgt,
+                           signed char* e_sdir, signed char* e_tdir, unsigned int* e_cov, unsigned char* e_alive,
+                           const ClearList* side);
 
 // one launch that zeroes up to 8 device ranges (a hipMemsetAsync is a kernel launch of its own: ~5 us
 // each, and a build issued ~40 of them); sizes are rounded up to 4 bytes — pad the allocations

@@ -343,13 +343,12 @@ int ensure_live_adj(amg_ctx* c) {
   AMGCHK(c->ladj_rows.ensure((size_t)(rows + 2) * sizeof(int4)));
   AMGCHK(c->ladj_pos.ensure((size_t)(E + 2) * sizeof(long long)));
   unsigned long long* ctr = c->status.as<unsigned long long>() + ST_COMPACT_A;  // [0] entries handed out, [1] long rows
-  {
+  {  // the rows and counters are zeroed by the scan's workgroups
     ClearList cl;
     cl.add(c->ladj_rows.p, (size_t)(rows + 2) * sizeof(int4));
     cl.add(ctr, 2 * sizeof(unsigned long long));
-    AMGCHK(clear_many(c, cl));
+    AMGCHK(prim_exscan_bytes_set(c, c->edge_alive.as<unsigned char>(), c->ladj_pos.as<long long>(), (size_t)E, &cl));
   }
-  AMGCHK(prim_exscan_bytes_set(c, c->edge_alive.as<unsigned char>(), c->ladj_pos.as<long long>(), (size_t)E));
   long long total = 0;
   {
     FetchList l;

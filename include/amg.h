@@ -437,6 +437,16 @@ int amg_last_timings(amg_ctx* ctx, const char** names, float* ms, int cap);
  * off amg_last_timings returns 0 stages. */
 int amg_set_timing(amg_ctx* ctx, int on);
 
+/* ---- tests: one device scan on host arrays --------------------------------------- */
+/* kind 0: out[i] = bytes set in in[0 .. i) for i <= n (uint8 in[n]); aux (n bytes) is zeroed on the side of the scan.
+ * 1: out[i] = sum of the edge-class widths before class i (uint64 pair keys in[n]: 1 for a self-loop, else 2).
+ * 2: out[i] = set flag bytes before word i (uint8 in[32 n]); aux = the n bitmap words (uint32).
+ * 3: in = kill[n] then alive[n] (uint8): out[i] = live killed nodes before i; aux = kill[n], alive[n] after.
+ * 4: in = uint32 len[n]: out[0 .. n] = exscan(len != 0), out[n + 1 .. 2n + 1] = exscan(len).
+ * 5: in = keys[n] (uint64), first[n] (uint64), cnt[n] (uint32): out[0] = directed edges, aux = src, tgt (int32),
+ *    cov (uint32), sdir, tdir (int8), alive (uint8) over 2n edges each. */
+int amg_scan_probe(amg_ctx* ctx, int kind, const void* in, int64_t n, int64_t* out, void* aux);
+
 #ifdef __cplusplus
 }
 #endif
