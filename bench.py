@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — read -> corrected gene-mer graph hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3-sweep|cfg3|cfg2|cfg4] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3-sweep|cfg3|cfg2|cfg4] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic gene calls whose CSR
 token arrays (and gene positions) are already resident in HBM:
@@ -14,11 +14,15 @@ token arrays (and gene positions) are already resident in HBM:
   cfg4       1 M error-free reads with 10 planted multi-copy AMR genes, k=5: build +
              assign_reads_to_genes through the reference-shaped Python API (configs[3])
 Prints ONE JSON line (driver contract): `value` is the device-resident rate (inputs in HBM when
-the clock starts, nothing read back); `e2e` (N = 1) is SURVEY 8(d)'s timed region — host CSR arrays
--> host graph arrays, H2D and D2H inside the clock, pinned buffers, the position upload overlapped
-with the first build on a second stream; `roofline` prices the dominant kernel with HIP events of
-the engine's own stream; `cpu_baseline` (sequential C restatement), `cpu_baseline_python` (the reference's cost
-model) and `cpu_baseline_ncore` time the CPU oracles on this box.
+the clock starts, nothing read back).  A plain run does only what that figure needs: set up, W warm-up
+steps, the step the full line instruments (uninstrumented), the K timed steps, --dump-outputs.
+`--full` adds everything else, each beside the headline: `roofline` prices the dominant kernel with
+HIP events of the engine's own stream in that instrumented step (+ `stages_ms_per_step`); `e2e`
+(N = 1) is SURVEY 8(d)'s timed region — host CSR arrays -> host graph arrays, H2D and D2H inside the
+clock, pinned buffers, the position upload overlapped with the first build on a second stream;
+`fused_first_filter`, `api_e2e`, `front_end`, `multi_k`, `bubbles` and `cfg4` measure other paths
+and sizes; `cpu_baseline` (sequential C restatement), `cpu_baseline_python` (the reference's cost
+model) and `cpu_baseline_ncore` time the CPU oracles on the host.
 Multi-GPU (torch.distributed.run, one rank per GPU, RCCL): every rank holds its own N-read
 shard of the global stream (weak scaling); EVERY build of the step merges the per-shard node /
 edge tables by key owner (all-to-all + all-gather, amira_amd/dist.py), so all ranks hold the
@@ -358,12 +362,13 @@ def run_cfg4(args, w, rank, world, local_rank):
 
     def step(record):
         from amira_amd import Engine
+        instrument = record and args.full   # (a plain run records the step's result, not its kernels)
         t0 = time.perf_counter()
         g = GeneMerGraph(reads, k, positions)
         t1 = time.perf_counter()
-        dev_ms = sum(m for _, m in g._engine.timings()) if record else 0.0
+        dev_ms = sum(m for _, m in g._engine.timings()) if instrument else 0.0
         plain_match = Engine.match_patterns
-        if record:   # the device searches of the clustering (k_match), call by call
+        if instrument:   # the device searches of the clustering (k_match), call by call
             note(g._engine)
 
             def timed_match(self, which, patterns):
@@ -371,7 +376,7 @@ def run_cfg4(args, w, rank, world, local_rank):
                 note(self)
                 return out
             Engine.match_patterns = timed_match
-        g._engine.set_timing(bool(record))
+        g._engine.set_timing(bool(instrument))
         try:
             clustered, path_reads = g.assign_reads_to_genes(genes, 1, {}, None)
         finally:
@@ -405,11 +410,13 @@ def run_cfg4(args, w, rank, world, local_rank):
                    "genes_of_interest": genes, "nodes": info.get("nodes"),
                    "alleles_found": sum(len(v) for v in info.get("alleles", {}).values()),
                    "allele_sizes": info.get("alleles")},
-        "stages_s_per_step": {"build_incl_h2d_and_view": round(float(np.mean(stage["build_s"])), 4),
-                              "device_build_ms": round(float(np.mean(stage["device_build_ms"])), 3),
-                              "assign_reads_to_genes": round(float(np.mean(stage["cluster_s"])), 4)},
+        "stages_s_per_step": None,
         "roofline": None,
     }
+    if args.full:   # (the stages of the instrumented step; dev_stages stays empty otherwise, and `roofline` null)
+        out["stages_s_per_step"] = {"build_incl_h2d_and_view": round(float(np.mean(stage["build_s"])), 4),
+                                    "device_build_ms": round(float(np.mean(stage["device_build_ms"])), 3),
+                                    "assign_reads_to_genes": round(float(np.mean(stage["cluster_s"])), 4)}
     # the device side of the step: the build's table passes and the batched sub-list searches of the clustering
     # (k_match: every pass reads the gene calls of all reads once — SURVEY 8(d)'s B_cluster term, 4 L bytes per read
     # and pass); the dominant one is priced against the HBM roofline, the rest listed
@@ -931,13 +938,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)   # (a fresh box runs its first steps 3 % slower)
     ap.add_argument("--workload", default="cfg3-sweep", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the instrumented step's `roofline` and stage "
+                         "times, the CPU baselines, `fused_first_filter`, `e2e`, `api_e2e`, `front_end`, `multi_k`, "
+                         "`bubbles`, `cfg4` (the --no-* options below leave some out); a plain run times the steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--full-cpu-baseline", action="store_true",
-                    help="cpu_baseline_python on SURVEY 8(d)'s full 1 %% read sample (~100 s of one core) instead of the "
-                         "~12 s sample of the default line")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-cfg4", action="store_true", help="skip the extra `cfg4` object (read-path clustering) of the default line")
-    ap.add_argument("--no-fused-line", action="store_true", help="skip the extra `fused_first_filter` measurement")
+                    help="--full, with cpu_baseline_python on SURVEY 8(d)'s full 1 %% read sample (~100 s of one core) "
+                         "instead of the ~12 s sample")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full without `e2e`, `api_e2e`, `front_end`, `multi_k`, `bubbles` and `cfg4`")
+    ap.add_argument("--no-cfg4", action="store_true", help="--full without the extra `cfg4` object (read-path clustering)")
+    ap.add_argument("--no-fused-line", action="store_true", help="--full without the extra `fused_first_filter` measurement")
     ap.add_argument("--no-merge", action="store_true", help="N > 1: independent shards, no table merge")
     ap.add_argument("--fused-filter", action="store_true",
                     help="sweep: first build and filter_graph(3,1) as one device pass (amg_build_filtered), as the "
@@ -949,6 +961,7 @@ def main():
                     help="after the timed steps, write what the last one computed (rank 0: the final graph and the node "
                          "of every window) as DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    args.full = args.full or args.full_cpu_baseline
     w = WORKLOADS[args.workload]
 
     if args.gpus < 1:
@@ -967,20 +980,20 @@ def main():
                  f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...) "
                  f"or call bench.py --gpus {args.gpus} without a launcher and it starts them itself")
 
-    # CPU yardsticks first (rank 0, N = 1), before this process touches the GPU: the N-core line
+    # CPU yardsticks first (rank 0, N = 1, --full), before this process touches the GPU: the N-core line
     # starts worker processes
+    cpu_yardsticks = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "cfg4":
+    if cpu_yardsticks and args.workload != "cfg4":
         cpu["cpu_baseline"] = cpu_baseline_c(w)
         cpu["cpu_baseline_python"] = cpu_baseline(w, budget_s=1e9) if args.full_cpu_baseline else cpu_baseline(w)
         cpu["cpu_baseline_ncore"] = cpu_baseline_ncore(w)
 
     cpu4 = None
-    if (rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "cfg3-sweep" and not args.no_cfg4
-            and not args.no_e2e):
+    if cpu_yardsticks and args.workload == "cfg3-sweep" and not args.no_cfg4 and not args.no_e2e:
         cpu4 = cpu_baseline_cfg4(WORKLOADS["cfg4"])
     if args.workload == "cfg4":
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if cpu_yardsticks:
             cpu = {"cpu_baseline": cpu_baseline_cfg4(w)}
         out = run_cfg4(args, w, rank, world, local_rank)
         out.update(cpu)
@@ -1099,8 +1112,9 @@ def main():
 
     for _ in range(args.warmup):
         step(False)
-    # one instrumented step outside the timed region (per-stage HIP-event times, counts)
-    step(True)
+    # one step outside the timed region, instrumented with --full (per-stage HIP-event times); either way the timed
+    # steps follow warmup + 1 steps
+    step(args.full)
     counts = eng.counts()
     if dist is not None:
         dist.barrier()
@@ -1125,7 +1139,7 @@ def main():
 
     # ---- the same sweep with its first two steps as one device pass (amg_build_filtered): reported beside `value`
     fused_line = None
-    if w["sweep"] and world == 1 and not merge and not args.fused_filter and not args.no_fused_line:
+    if args.full and w["sweep"] and world == 1 and not merge and not args.fused_filter and not args.no_fused_line:
         args.fused_filter = True
         for _ in range(max(args.warmup, 1)):
             step(False)
@@ -1144,7 +1158,7 @@ def main():
 
     # ---- SURVEY 8(d)'s timed region: host CSR -> host graph arrays (N = 1)
     e2e = None
-    if world == 1 and not merge and not args.no_e2e:
+    if args.full and world == 1 and not merge and not args.no_e2e:
         pin = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
         h_toks, h_offs = pin(toks), pin(offs)
         T = len(toks)
@@ -1244,11 +1258,11 @@ def main():
     # ---- the same sweep through the reference-shaped Python API (amira_amd.graph_utils / GeneMerGraph), inputs as
     # array-backed mappings (amira_amd.io): what a caller of the drop-in pays per cleaning iteration, PCIe included
     api_e2e = None
-    if w["sweep"] and world == 1 and not merge and not args.no_e2e:
+    if args.full and w["sweep"] and world == 1 and not merge and not args.no_e2e:
         api_e2e = run_api_e2e(w, vocab, toks, offs, k, n_windows)
 
     front_end = multi_k = bubbles = None
-    if w["sweep"] and world == 1 and not merge and not args.no_e2e and rank == 0:
+    if args.full and w["sweep"] and world == 1 and not merge and not args.no_e2e and rank == 0:
         for name, fn in (("front_end", lambda: run_front_end(w, vocab, toks, offs, k, n_windows)),
                          ("multi_k", lambda: run_multi_k(w, vocab, toks, offs, local_rank)),
                          ("bubbles", lambda: run_bubbles(local_rank, with_cpu=not args.no_cpu_baseline))):
@@ -1265,6 +1279,27 @@ def main():
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "gene-mers/s to corrected GeneMerGraph" if w["sweep"] else "gene-mers/s to GeneMerGraph (build + coverage)",
+            "value": world * n_windows * args.steps / dt, "unit": "gene-mers/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+            "reads_per_s": world * N * args.steps / dt,
+            "config": {"workload": w["desc"] + ("; first build and filter_graph(3,1) as one device pass (--fused-filter)"
+                                                 if (args.fused_filter and w["sweep"] and not merge) else ""),
+                       "timed_region": "device-resident: inputs in HBM when the clock starts, nothing read back "
+                                       "(`e2e`, with --full, is SURVEY 8(d)'s host-to-host region)",
+                       "reads_per_gpu": N, "genes_per_read": L, "k": k,
+                       "vocab": w["V"], "error_rate": w["err"], "gene_mers_per_gpu": n_windows,
+                       "final_nodes": counts["n_nodes"], "final_edges": counts["n_edges"],
+                       "shared_gpu_functional_test_only": True if shared_gpu else None,
+                       "multi_gpu": ("n/a" if not (world > 1 or merge) else
+                                     "read shards + key-owner table merge per build (RCCL all-to-all + all-gather)"
+                                     if merge else "independent read shards, no table merge")},
+            "roofline": None,
+        }
+    if rank == 0 and args.full:
         stage_avg = {n: v[0] / v[1] for n, v in stage_ms.items()}     # ms per launch
         stage_tot = {n: v[0] for n, v in stage_ms.items()}            # ms per step
         n_gapped = info.get("marked_reads", 0)
@@ -1330,43 +1365,24 @@ def main():
                                 "the slot probes), separate --pmc passes, from profiles/" + os.path.basename(pmc_path))
             except Exception:  # noqa: BLE001
                 traffic = None
-        out = {
-            "metric": "gene-mers/s to corrected GeneMerGraph" if w["sweep"] else "gene-mers/s to GeneMerGraph (build + coverage)",
-            "value": world * n_windows * args.steps / dt, "unit": "gene-mers/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-            "reads_per_s": world * N * args.steps / dt,
-            "config": {"workload": w["desc"] + ("; first build and filter_graph(3,1) as one device pass (--fused-filter)"
-                                                 if (args.fused_filter and w["sweep"] and not merge) else ""),
-                       "timed_region": "device-resident: inputs in HBM when the clock starts, nothing read back "
-                                       "(`e2e` is SURVEY 8(d)'s host-to-host region)",
-                       "reads_per_gpu": N, "genes_per_read": L, "k": k,
-                       "vocab": w["V"], "error_rate": w["err"], "gene_mers_per_gpu": n_windows,
-                       "final_nodes": counts["n_nodes"], "final_edges": counts["n_edges"],
-                       "shared_gpu_functional_test_only": True if shared_gpu else None,
-                       "multi_gpu": ("n/a" if not (world > 1 or merge) else
-                                     "read shards + key-owner table merge per build (RCCL all-to-all + all-gather)"
-                                     if merge else "independent read shards, no table merge")},
-            "roofline": {"bound": "hbm", "kernel": kernel_of[dom], "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_note": traffic_note,
-                         "algorithmic_bytes_per_launch": cands[dom],
-                         "avg_launch_ms": stage_avg[dom], "launches_per_step": stage_ms[dom][1],
-                         # every launch of the step on its own (a cleaning sweep: the first build's pass over uncorrected
-                         # reads creates 5.4 M keys, the rebuild's finds nearly all of its keys; the third graph of the
-                         # sweep is made from the second one's live part and has no table pass at all)
-                         "launch_ms": [round(x, 4) for x in stage_each.get(dom, [])],
-                         "launch_frac": [round(cands[dom] / (x * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) for x in stage_each.get(dom, []) if x > 0],
-                         "largest_stages": per_kernel,
-                         "table_passes": table_passes,
-                         "whole_sweep": whole_sweep,
-                         "whole_build": {"algorithmic_bytes_per_gene_mer": survey_b,
-                                         "ms_per_build": build_ms / n_builds,
-                                         "achieved": survey_b * n_windows / (build_ms / n_builds * 1e-3) / 1e9,
-                                         "unit": "GB/s"}},
-            "stages_ms_per_step": {n: round(v, 3) for n, v in stage_tot.items()},
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": kernel_of[dom], "achieved": achieved,
+                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": traffic, "traffic_note": traffic_note,
+                           "algorithmic_bytes_per_launch": cands[dom],
+                           "avg_launch_ms": stage_avg[dom], "launches_per_step": stage_ms[dom][1],
+                           # every launch of the step on its own (a cleaning sweep: the first build's pass over uncorrected
+                           # reads creates 5.4 M keys, the rebuild's finds nearly all of its keys; the third graph of the
+                           # sweep is made from the second one's live part and has no table pass at all)
+                           "launch_ms": [round(x, 4) for x in stage_each.get(dom, [])],
+                           "launch_frac": [round(cands[dom] / (x * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) for x in stage_each.get(dom, []) if x > 0],
+                           "largest_stages": per_kernel,
+                           "table_passes": table_passes,
+                           "whole_sweep": whole_sweep,
+                           "whole_build": {"algorithmic_bytes_per_gene_mer": survey_b,
+                                           "ms_per_build": build_ms / n_builds,
+                                           "achieved": survey_b * n_windows / (build_ms / n_builds * 1e-3) / 1e9,
+                                           "unit": "GB/s"}}
+        out["stages_ms_per_step"] = {n: round(v, 3) for n, v in stage_tot.items()}
         if fused_line is not None:
             out["fused_first_filter"] = fused_line
         if e2e is not None:
@@ -1381,10 +1397,10 @@ def main():
             out["bubbles"] = bubbles
         out.update(cpu)
     # ---- BASELINE configs[3] beside it: build + read-path clustering through the Python API (its own engine)
-    if rank == 0 and world == 1 and not merge and w["sweep"] and not args.no_cfg4 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not merge and w["sweep"] and not args.no_cfg4 and not args.no_e2e:
         eng.close()
         eng = None
-        c4 = run_cfg4(argparse.Namespace(steps=2, warmup=1), WORKLOADS["cfg4"], 0, 1, local_rank)
+        c4 = run_cfg4(argparse.Namespace(steps=2, warmup=1, full=True), WORKLOADS["cfg4"], 0, 1, local_rank)
         out["cfg4"] = {key: c4[key] for key in ("metric", "value", "unit", "ms_per_step", "steps", "reads_per_s",
                                                  "config", "stages_s_per_step", "roofline")}
         if cpu4 is not None:

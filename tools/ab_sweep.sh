@@ -1,12 +1,13 @@
 #!/bin/bash
 # usage: tools/ab_sweep.sh <tag> ["ENV=1 ENV2=x" ...] — the cfg 3 sweep once per environment (A/B switches), one line each:
-# ms per sweep and the per-stage HIP-event times of the instrumented step
+# ms per sweep and the per-stage HIP-event times of the instrumented step (bench.py --full); lines in $OUT/ab_<tag>.txt
 tag=$1; shift
-cd $GRAFT_REPO_ROOT
+out=$(realpath "${OUT:-.}")
+cd "$(dirname "$0")/.."
 [ $# -eq 0 ] && set -- ""
 for e in "$@"; do
-  env $e timeout 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-cfg4 --no-fused-line 2>/dev/null | tail -1 > gpurun_out/ab_${tag}.tmp
-  python3 - "$e" gpurun_out/ab_${tag}.tmp >> gpurun_out/ab_${tag}.txt <<'PY'
+  env $e timeout 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-cfg4 --no-fused-line 2>/dev/null | tail -1 > "$out/ab_${tag}.tmp"
+  python3 - "$e" "$out/ab_${tag}.tmp" >> "$out/ab_${tag}.txt" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[2]))
@@ -17,5 +18,5 @@ except Exception as e:
     print(f"[{sys.argv[1]}] FAILED {e}: {open(sys.argv[2]).read()[:300]}")
 PY
 done
-rm -f gpurun_out/ab_${tag}.tmp
-cat gpurun_out/ab_${tag}.txt
+rm -f "$out/ab_${tag}.tmp"
+cat "$out/ab_${tag}.txt"

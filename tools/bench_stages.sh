@@ -1,10 +1,11 @@
 #!/bin/bash
-# usage: tools/bench_stages.sh <tag>  — sweep + build benches, stage table
+# usage: tools/bench_stages.sh <tag>  — sweep + build benches (bench.py --full), stage table; the lines in $OUT
 tag=$1
-timeout 150 python bench.py --steps 5 --warmup 1 2>&1 | tail -1 > gpurun_out/${tag}_sweep.json
-timeout 150 python bench.py --workload cfg3 --steps 5 --warmup 1 2>&1 | tail -1 > gpurun_out/${tag}_build.json
-python - <<PY
-import json
+out=${OUT:-.}
+timeout 600 python bench.py --full --steps 5 --warmup 1 2>&1 | tail -1 > "$out/${tag}_sweep.json"
+timeout 600 python bench.py --full --workload cfg3 --steps 5 --warmup 1 2>&1 | tail -1 > "$out/${tag}_build.json"
+python - "$out" <<PY
+import json, os, sys
 for f in ("${tag}_sweep","${tag}_build"):
-    d=json.load(open("gpurun_out/%s.json"%f)); print(f, round(d["ms_per_step"],3), d["stages_ms_per_step"])
+    d=json.load(open(os.path.join(sys.argv[1], "%s.json"%f))); print(f, round(d["ms_per_step"],3), d["stages_ms_per_step"])
 PY

@@ -17,10 +17,10 @@ cd $R
 python3 tools/pmc_fetch_write.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE > $O/${tag}_sweep_pmc_summary.json
 # the summary has to be in profiles/ for bench.py to report roofline.traffic from it
 cp $O/${tag}_sweep_pmc_summary.json $R/profiles/${tag}_sweep_pmc_summary.json
-timeout 600 python3 bench.py --steps 10 --warmup 2 | tail -1 > $O/${tag}_bench_cfg3_sweep.json
-timeout 300 python3 bench.py --workload cfg3 --steps 10 --warmup 2 --no-e2e | tail -1 > $O/${tag}_bench_cfg3_build.json
-timeout 300 python3 bench.py --workload cfg2 --steps 20 --warmup 2 --no-e2e | tail -1 > $O/${tag}_bench_cfg2.json
-timeout 600 python3 bench.py --workload cfg4 --steps 2 --warmup 1 | tail -1 > $O/${tag}_bench_cfg4.json
-timeout 300 python3 bench.py --steps 10 --warmup 2 --force-merge --no-cpu-baseline --no-e2e | tail -1 > $O/${tag}_bench_cfg3_sweep_merged_n1.json
+timeout 600 python3 bench.py --full --steps 10 --warmup 2 | tail -1 > $O/${tag}_bench_cfg3_sweep.json
+timeout 300 python3 bench.py --full --workload cfg3 --steps 10 --warmup 2 --no-e2e | tail -1 > $O/${tag}_bench_cfg3_build.json
+timeout 300 python3 bench.py --full --workload cfg2 --steps 20 --warmup 2 --no-e2e | tail -1 > $O/${tag}_bench_cfg2.json
+timeout 600 python3 bench.py --full --workload cfg4 --steps 2 --warmup 1 | tail -1 > $O/${tag}_bench_cfg4.json
+timeout 300 python3 bench.py --full --steps 10 --warmup 2 --force-merge --no-cpu-baseline --no-e2e | tail -1 > $O/${tag}_bench_cfg3_sweep_merged_n1.json
 rm -rf $O/ks $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 ls -la $O
