@@ -355,13 +355,6 @@ extern "C" int amg_counts(amg_ctx* c, amg_counts_t* o) {
   return AMG_OK;
 }
 
-#define NEED_BUILT(c)                                                     \
-  do {                                                                    \
-    if (!(c)) return amg_fail(AMG_E_ARG, "null ctx");                     \
-    if (!(c)->built) return amg_fail(AMG_E_STATE, "amg_build first");     \
-    HIPCHK(hipSetDevice((c)->device));                                    \
-  } while (0)
-
 static int d2h(amg_ctx* c, void* dst, const DevBuf& src, size_t bytes) {
   if (!dst || bytes == 0) return AMG_OK;
   HIPCHK(hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, c->stream));

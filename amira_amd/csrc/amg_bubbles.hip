@@ -20,18 +20,6 @@
 
 #include <algorithm>
 
-#define NEED_BUILT(c)                                                     \
-  do {                                                                    \
-    if (!(c)) return amg_fail(AMG_E_ARG, "null ctx");                     \
-    if (!(c)->built) return amg_fail(AMG_E_STATE, "amg_build first");     \
-    HIPCHK(hipSetDevice((c)->device));                                    \
-  } while (0)
-
-static inline unsigned int nblk(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
-
 struct BubbleState {
   // amg_junction_paths -> amg_get_junction_paths
   std::vector<int> j_node;
@@ -92,7 +80,7 @@ __device__ __forceinline__ int bj_edges_between(const GView& g, int a, int b) {
 #define BJ_BUDGET 2ull   // a search was abandoned
 #define BJ_STEPS (1ull << 24)
 
-// One WAVE per start junction, the search run cooperatively as in amg_passes.hip (dfs_paths_wave): stack level d lives in
+// One WAVE per start junction, the search run cooperatively as in amg_correct_gapped.hip (dfs_paths_wave): stack level d lives in
 // lane d.  A node entered at depth d >= 1 with L = d + 1 <= distance nodes on the path that is a junction on the side the
 // path arrives at is a record {stop junction, the L nodes and directions}; EMIT = false counts records and path nodes,
 // EMIT = true writes them behind the start's share of the pools — in search order, which is the order the reference's

@@ -673,10 +673,7 @@ int bs_count_by_slot(amg_ctx* c, const int* slots, int* ids_scratch, long long n
 //   bs_edges_pass        local adjacencies -> local edge-class table (+ compaction list)
 //   bs_pairs_from_local  single GPU: edge classes in first-seen order as arrays
 //   bs_finish_from_pairs directed edges, components, adjacency lists
-static inline unsigned int blocks_for(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
+#define blocks_for nblk  // (amg_internal.h)
 
 static int read_status(amg_ctx* c, unsigned long long* host) {
   return fetch_status(c, host);

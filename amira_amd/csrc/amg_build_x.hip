@@ -780,10 +780,7 @@ __global__ void k_x_gather_pairs(const unsigned int* __restrict__ first_sorted,
 #define X_CTRS (F_SHARDS + 1)  // counters of a plain pass: F_SHARDS shards + the first tiles'
 
 // ------------------------------------------------------------------ host side
-static inline unsigned int blocks_for(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
+#define blocks_for nblk  // (amg_internal.h)
 
 static const unsigned int kProbeLimitX = 1024;
 

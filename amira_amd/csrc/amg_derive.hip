@@ -19,11 +19,6 @@
 // AMG_NO_DERIVE=1: A/B + test switch.
 #include "amg_device.h"
 
-static inline unsigned int nblk(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
-
 // new token index of the old token t (the first token of a kept window): the new read whose slice holds it
 __device__ __forceinline__ long long dv_new_token(long long t, const long long* __restrict__ src,
                                                   const long long* __restrict__ read_off, long long n_reads, int k,

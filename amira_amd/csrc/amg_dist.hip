@@ -44,11 +44,6 @@
     HIPCHK(hipSetDevice((c)->device));                           \
   } while (0)
 
-static inline unsigned int nblk(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
-
 #define REC_BYTES 24    // {u64 merge key, u64 first-seen, u32 count, u32 pad}: what travels to the owners (both kinds)
 #define REPLY_WORDS 2   // {u64 global first-seen | REPLY_DROPPED, u64 total count}: what comes back per record
 // held records are arrays of 32-bit words (they are the bytes of the all-gathers: 20 + 24 bytes per class + node of a

@@ -139,7 +139,7 @@ struct amg_ctx {
   DevBuf gene_end;    // int64[n_tokens]
   DevBuf read_len;    // int64[n_reads]
   bool have_pos = false, have_read_len = false;
-  // where the positions of the CURRENT reads' genes are (amg_passes.hip, CorrArgs): offsets into
+  // where the positions of the CURRENT reads' genes are (amg_correct.h, CorrArgs): offsets into
   // gene_start / gene_end as handed to amg_set_positions (pos_n0 entries) or, from pos_n0 on, into
   // the pool of positions the carry-over kernels produced
   DevBuf pos_off, c_pos_off;   // int64[n_reads] (pos_identity: the read's token offset, array unused)
@@ -270,7 +270,7 @@ struct amg_ctx {
   DevBuf s0, s1, s2, s3, s4, s5;  // general scratch arrays
   DevBuf nw_big;       // global scratch of the general position carry-over kernel (long reads)
   DevBuf gap_rec;      // per gapped read: the record k_corr_gapped_fast starts from
-  // path memo of the re-threading (amg_passes.hip: k_gap_queries / k_gap_dfs)
+  // path memo of the re-threading (amg_correct_gapped.hip: k_gap_queries / k_gap_dfs)
   DevBuf gm_mask;      // uint64[n_reads]   live-window mask per read (k_corr_classify)
   DevBuf gm_tab;       // uint64[slots]     question table: (start node, direction, end node)
   DevBuf gm_res;       // int4  [slots]     per question {pool offset, ints, paths}
@@ -365,7 +365,7 @@ void stage_begin(amg_ctx* c, const char* name);
 void stage_end(amg_ctx* c);
 void stages_reset(amg_ctx* c);
 
-// ------------------------------------------------------------------ walkers' view of the live graph (amg_passes.hip)
+// ------------------------------------------------------------------ walkers' view of the live graph (amg_filter.hip)
 struct GView {
   // live adjacency: row 2n = forward list of node n, row 2n+1 = backward list, only ALIVE
   // edges, in list order, with the target inline (.x = target node, .y = target direction)
@@ -427,6 +427,20 @@ int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal);
 int bx_components_from_claims(amg_ctx* c);
 int bs_count_by_slot(amg_ctx* c, const int* slots, int* ids_scratch, long long n, Slot* tab,
                      const unsigned int* slot_sorted, long long n_ids, unsigned int* out, int kind);
+
+// entry points that need a built graph start with this
+#define NEED_BUILT(c)                                                     \
+  do {                                                                    \
+    if (!(c)) return amg_fail(AMG_E_ARG, "null ctx");                     \
+    if (!(c)->built) return amg_fail(AMG_E_STATE, "amg_build first");     \
+    HIPCHK(hipSetDevice((c)->device));                                    \
+  } while (0)
+
+// blocks of `per` items that cover n items, at least one (a grid of zero blocks is a launch error)
+static inline unsigned int nblk(long long n, int per) {
+  long long b = (n + per - 1) / per;
+  return (unsigned int)(b < 1 ? 1 : b);
+}
 
 static inline int ilog2_ceil(uint64_t x) {
   int b = 0;

@@ -11,11 +11,6 @@
 
 #include "amg_device.h"
 
-static inline unsigned int nblk(long long n, int per) {
-  long long b = (n + per - 1) / per;
-  return (unsigned int)(b < 1 ? 1 : b);
-}
-
 #define POS_BITS 20
 #define READ_BITS 28
 #define PAT_BITS 16

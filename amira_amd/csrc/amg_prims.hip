@@ -2,7 +2,7 @@
 // rocPRIM does the generic sorting of SMALL arrays (distinct nodes, edge
 // classes); every gene-mer-sized kernel (window extraction, hashing, table upsert,
 // compaction, masking, threading, matching) is hand-written in amg_build.hip /
-// amg_passes.hip.  Kept in its own translation unit because it dominates compile time.
+// amg_filter.hip.  Kept in its own translation unit because it dominates compile time.
 #include "amg_internal.h"
 
 #include <rocprim/rocprim.hpp>

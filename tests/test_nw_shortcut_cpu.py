@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 
 
 def shortcut_says_diagonal(x, y):
-    """the rule of amg_passes.hip (k_corr_nw_fast, 'shortcut')"""
+    """the rule of amg_correct_nw.hip (k_corr_nw_fast, 'shortcut')"""
     n = len(x)
     if n != len(y):
         return False
