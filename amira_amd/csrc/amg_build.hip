@@ -1,8 +1,7 @@
 // amg_build.hip — GeneMerGraph.__init__ on the device (reference construct_graph.py:31-102).
 //
-// Launch sequence of amg_build (all on ctx->stream):
-//   k_read_stats      per-read window / short-read counts          (construct_graph.py:53-55)
-//   k_tile_reads      first read boundary of every token tile
+// Launch sequence of amg_build on the 32-byte-slot path, all on ctx->stream (most builds take amg_build_x.hip's: build_impl):
+//   k_read_stats      per-read window / short-read counts, read-end bitmap (construct_graph.py:53-55)
 //   k_node_upsert     K1+K2: LDS-staged sliding windows, canonical orientation
 //                     (construct_gene_mer.py:4-56), fingerprint, open-address upsert:
 //                     count (+=1, construct_node.py:33-36) and first-seen (atomicMax of ~first)
@@ -667,25 +666,19 @@ int bs_count_by_slot(amg_ctx* c, const int* slots, int* ids_scratch, long long n
 
 // ------------------------------------------------------------------ host orchestration
 // The build is split into stages so that the multi-GPU path (amg_dist.hip) can put its
-// exchanges between them:
+// exchanges between them.  Node and edge-class arrays come from the 16-byte slots of amg_build_x.hip (bx_nodes /
+// bx_nodes_filtered, bx_edges) whenever bx_applicable, else (2^29 tokens and more, a merged build whose tuple does not
+// fit a slot, AMG_KEY_MODE=fp, AMG_COUNT_INLINE, a fitting tuple under the weak-fingerprint hook) from 32-byte slots:
 //   bs_nodes_pass        local windows -> local node table (+ compaction list in s1 / s3)
 //   bs_nodes_rank_local  single GPU: node ids from the local table
 //   bs_edges_pass        local adjacencies -> local edge-class table (+ compaction list)
 //   bs_pairs_from_local  single GPU: edge classes in first-seen order as arrays
-//   bs_finish_from_pairs directed edges, components, adjacency lists
-#define blocks_for nblk  // (amg_internal.h)
-
-static int read_status(amg_ctx* c, unsigned long long* host) {
-  return fetch_status(c, host);
-}
-
+// and either way bs_finish_from_pairs: directed edges (components, adjacency lists: on demand, ensure_*)
 uint64_t pow2_at_least(uint64_t x) {
   uint64_t p = 1024;
   while (p < x) p <<= 1;
   return p;
 }
-
-static const unsigned int kProbeLimit = 1024;
 
 // window / short-read counts into the status words + the read-end bitmap the tile kernels use
 int bs_read_stats(amg_ctx* c, int k, const ClearList* also) {
@@ -701,16 +694,16 @@ int bs_read_stats(amg_ctx* c, int k, const ClearList* also) {
     AMGCHK(clear_many(c, cl));
   }
   if (R > 0)
-    hipLaunchKernelGGL(k_read_stats, dim3(blocks_for(R, 256) < 512u ? blocks_for(R, 256) : 512u), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_read_stats, dim3(nblk(R, 256) < 512u ? nblk(R, 256) : 512u), dim3(256), 0, st,
                        c->read_off.as<long long>(), R, T, k, c->status.as<unsigned long long>(),
                        c->bnd_bits.as<unsigned int>());
   stage_end(c);
   return AMG_OK;
 }
 
-// returns AMG_OK, or AMG_E_OVERFLOW with *which = 1 (node table too small)
-int bs_nodes_pass(amg_ctx* c, int k, int* which) {
-  *which = 0;
+// returns AMG_OK, or AMG_E_OVERFLOW with *which = OV_NODE_TABLE (node table too small)
+int bs_nodes_pass(amg_ctx* c, int k, Overflow* which) {
+  *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens;
   unsigned long long hs[ST_WORDS];
@@ -746,21 +739,18 @@ int bs_nodes_pass(amg_ctx* c, int k, int* which) {
   AMGCHK(c->s2.ensure(max_nodes * sizeof(unsigned long long)));
   AMGCHK(c->s3.ensure(max_nodes * sizeof(unsigned int)));
   AMGCHK(c->s4.ensure(max_nodes * sizeof(unsigned int)));
-  hipLaunchKernelGGL(k_compact_slots, dim3(blocks_for(c->node_slots, 2048)), dim3(256), 0, st,
+  hipLaunchKernelGGL(k_compact_slots, dim3(nblk(c->node_slots, 2048)), dim3(256), 0, st,
                      c->node_tab.as<Slot>(), (unsigned long long)c->node_slots,
                      c->s1.as<unsigned long long>(), c->s3.as<unsigned int>(),
                      c->status.as<unsigned long long>() + ST_COMPACT_A);
-  AMGCHK(read_status(c, hs));
+  AMGCHK(fetch_status(c, hs));
   stage_end(c);
   if (hs[ST_BADINPUT])
     return amg_fail(AMG_E_ARG, hs[ST_BADINPUT] == 1 ? "read_offsets must start at 0, never decrease and end at the token count"
                                                     : "a token lies outside [0, two_v)");
   if (hs[ST_PALINDROME])
     return amg_fail(AMG_E_PALINDROME, "Gene-mer and reverse complement gene-mer are identical");
-  if (hs[ST_OVERFLOW]) {
-    *which = 1;
-    return AMG_E_OVERFLOW;
-  }
+  if (hs[ST_OVERFLOW]) return overflowed(which, OV_NODE_TABLE);
   c->n_windows = (int64_t)hs[ST_N_WINDOWS];
   c->n_short = (int64_t)hs[ST_N_SHORT];
   c->n_local_nodes = (int64_t)hs[ST_COMPACT_A];
@@ -788,7 +778,7 @@ int bs_nodes_rank_local(amg_ctx* c) {
                            first_bits));
   AMGCHK(bs_alloc_nodes(c, D));
   if (D > 0)
-    hipLaunchKernelGGL(k_assign_nodes, dim3(blocks_for(D, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st,
                        c->s2.as<unsigned long long>(), c->s4.as<unsigned int>(), D,
                        c->node_tab.as<Slot>(), c->tokens.as<int>(), c->k, c->two_v,
                        (long long)c->tok_base, c->packed_nodes ? 1 : 0, c->node_tokens.as<int>(),
@@ -798,9 +788,9 @@ int bs_nodes_rank_local(amg_ctx* c) {
   return AMG_OK;
 }
 
-// returns AMG_OK, or AMG_E_OVERFLOW with *which = 2 (edge table) / 3 (fingerprint collision)
-int bs_edges_pass(amg_ctx* c, int* which) {
-  *which = 0;
+// returns AMG_OK, or AMG_E_OVERFLOW with *which = OV_EDGE_TABLE / OV_COLLISION (fingerprint collision)
+int bs_edges_pass(amg_ctx* c, Overflow* which) {
+  *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens, D = c->n_nodes;
   const long long n_tiles = (T + TILE - 1) / TILE;
@@ -831,20 +821,14 @@ int bs_edges_pass(amg_ctx* c, int* which) {
   AMGCHK(c->s2.ensure(max_pairs * sizeof(unsigned long long)));
   AMGCHK(c->s3.ensure(max_pairs * sizeof(unsigned int)));
   AMGCHK(c->s4.ensure(max_pairs * sizeof(unsigned int)));
-  hipLaunchKernelGGL(k_compact_slots, dim3(blocks_for(c->edge_slots, 2048)), dim3(256), 0, st,
+  hipLaunchKernelGGL(k_compact_slots, dim3(nblk(c->edge_slots, 2048)), dim3(256), 0, st,
                      c->edge_tab.as<Slot>(), (unsigned long long)c->edge_slots,
                      c->s1.as<unsigned long long>(), c->s3.as<unsigned int>(),
                      c->status.as<unsigned long long>() + ST_COMPACT_B);
-  AMGCHK(read_status(c, hs));
+  AMGCHK(fetch_status(c, hs));
   stage_end(c);
-  if (hs[ST_COLLISION]) {
-    *which = 3;
-    return AMG_E_OVERFLOW;
-  }
-  if (hs[ST_OVERFLOW]) {
-    *which = 2;
-    return AMG_E_OVERFLOW;
-  }
+  if (hs[ST_COLLISION]) return overflowed(which, OV_COLLISION);
+  if (hs[ST_OVERFLOW]) return overflowed(which, OV_EDGE_TABLE);
   c->n_local_pairs = (int64_t)hs[ST_COMPACT_B];
   if (!c->count_inline && !c->dist_mode) {
     // node coverage (construct_node.py:33-36) from the per-window node ids
@@ -873,14 +857,14 @@ int bs_pairs_from_local(amg_ctx* c) {
                            c->s3.as<unsigned int>(), c->s4.as<unsigned int>(), (size_t)P,
                            efirst_bits));
   if (P > 0)
-    hipLaunchKernelGGL(k_gather_pairs, dim3(blocks_for(P, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_gather_pairs, dim3(nblk(P, 256)), dim3(256), 0, st,
                        c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot>(),
                        c->pair_key.as<unsigned long long>(), c->pair_cnt.as<unsigned int>());
   stage_end(c);
   if (!c->count_inline && P > 0) {
     // edge-class coverage: pair ids into the table, then count the per-adjacency slots
     stage_begin(c, "edge_count");
-    hipLaunchKernelGGL(k_set_pair_ids, dim3(blocks_for(P, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_set_pair_ids, dim3(nblk(P, 256)), dim3(256), 0, st,
                        c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot>());
     AMGCHK(count_ids(c, c->tok_pair.as<int>(), c->n_tokens, c->edge_tab.as<Slot>(), P,
                      c->pair_cnt.as<unsigned int>(), 1));
@@ -980,18 +964,18 @@ int ensure_components(amg_ctx* c) {
       ClearList cl;
       cl.add(starts, (size_t)D * sizeof(unsigned int), 1u);
       AMGCHK(clear_many(c, cl));
-      hipLaunchKernelGGL(k_uf_links, dim3(blocks_for(P, 256)), dim3(256), 0, st, c->pair_key.as<unsigned long long>(), P, starts);
+      hipLaunchKernelGGL(k_uf_links, dim3(nblk(P, 256)), dim3(256), 0, st, c->pair_key.as<unsigned long long>(), P, starts);
       AMGCHK(prim_exscan_u32_to_i64(c, starts, run_of, (size_t)D));
-      hipLaunchKernelGGL(k_uf_run_starts, dim3(blocks_for(D, 256)), dim3(256), 0, st, starts, run_of, D, run_start);
-      hipLaunchKernelGGL(k_uf_init_runs, dim3(blocks_for(D, 256)), dim3(256), 0, st, starts, run_of, run_start, D, parent);
-      hipLaunchKernelGGL(k_uf_union, dim3(blocks_for(P, 256)), dim3(256), 0, st,
+      hipLaunchKernelGGL(k_uf_run_starts, dim3(nblk(D, 256)), dim3(256), 0, st, starts, run_of, D, run_start);
+      hipLaunchKernelGGL(k_uf_init_runs, dim3(nblk(D, 256)), dim3(256), 0, st, starts, run_of, run_start, D, parent);
+      hipLaunchKernelGGL(k_uf_union, dim3(nblk(P, 256)), dim3(256), 0, st,
                          c->pair_key.as<unsigned long long>(), P, parent);
     } else {
-      hipLaunchKernelGGL(k_uf_init, dim3(blocks_for(D, 256)), dim3(256), 0, st, parent, D);
+      hipLaunchKernelGGL(k_uf_init, dim3(nblk(D, 256)), dim3(256), 0, st, parent, D);
     }
-    hipLaunchKernelGGL(k_uf_roots, dim3(blocks_for(D, 256)), dim3(256), 0, st, parent, D, is_root, root_copy);
+    hipLaunchKernelGGL(k_uf_roots, dim3(nblk(D, 256)), dim3(256), 0, st, parent, D, is_root, root_copy);
     AMGCHK(prim_exscan_u32_to_i64(c, is_root, c->s1.as<long long>(), (size_t)D + 1));
-    hipLaunchKernelGGL(k_uf_label, dim3(blocks_for(D, 256)), dim3(256), 0, st, root_copy,
+    hipLaunchKernelGGL(k_uf_label, dim3(nblk(D, 256)), dim3(256), 0, st, root_copy,
                        c->s1.as<long long>(), D, parent);
     FetchList l;
     l.add(c->s1.as<long long>() + D);
@@ -1030,12 +1014,12 @@ int ensure_adjacency(amg_ctx* c) {
       cl.add(n_long, sizeof(unsigned long long));
       AMGCHK(clear_many(c, cl));
     }
-    hipLaunchKernelGGL(k_adjc_ticket, dim3(blocks_for(E, 256)), dim3(256), 0, st, c->edge_src.as<int>(),
+    hipLaunchKernelGGL(k_adjc_ticket, dim3(nblk(E, 256)), dim3(256), 0, st, c->edge_src.as<int>(),
                        c->edge_sdir.as<signed char>(), E, cnt, tick);
     AMGCHK(prim_exscan_u32_to_i64(c, cnt, c->adj_off.as<long long>(), (size_t)(2 * D + 1)));
-    hipLaunchKernelGGL(k_adjc_fill, dim3(blocks_for(E, 256)), dim3(256), 0, st, c->edge_src.as<int>(),
+    hipLaunchKernelGGL(k_adjc_fill, dim3(nblk(E, 256)), dim3(256), 0, st, c->edge_src.as<int>(),
                        c->edge_sdir.as<signed char>(), E, c->adj_off.as<long long>(), tick, tmp);
-    hipLaunchKernelGGL(k_adjc_rows, dim3(blocks_for(2 * D, 256)), dim3(256), 0, st, c->adj_off.as<long long>(), 2 * D, tmp,
+    hipLaunchKernelGGL(k_adjc_rows, dim3(nblk(2 * D, 256)), dim3(256), 0, st, c->adj_off.as<long long>(), 2 * D, tmp,
                        c->adj_edge.as<int>(), long_rows, n_long);
     const long long hub_words = (E + 31) / 32 + 1;  // (scratch of the hub rows: HUB_BLOCKS bitmaps over the edge ids)
     AMGCHK(c->hub_bits.ensure((size_t)HUB_BLOCKS * (size_t)hub_words * sizeof(unsigned int)));
@@ -1046,7 +1030,7 @@ int ensure_adjacency(amg_ctx* c) {
     return AMG_OK;
   }
   if (E > 0) {
-    hipLaunchKernelGGL(k_adj_keys, dim3(blocks_for(E, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_adj_keys, dim3(nblk(E, 256)), dim3(256), 0, st,
                        c->edge_src.as<int>(), c->edge_sdir.as<signed char>(), E,
                        c->s1.as<unsigned int>(), c->s2.as<unsigned int>());
     AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s3.as<unsigned int>(),
@@ -1054,7 +1038,7 @@ int ensure_adjacency(amg_ctx* c) {
                              reinterpret_cast<unsigned int*>(c->adj_edge.p), (size_t)E,
                              ilog2_ceil((uint64_t)2 * D + 2) + 1));
   }
-  hipLaunchKernelGGL(k_row_offsets, dim3(blocks_for(E + 1, 256)), dim3(256), 0, st,
+  hipLaunchKernelGGL(k_row_offsets, dim3(nblk(E + 1, 256)), dim3(256), 0, st,
                      c->s3.as<unsigned int>(), E, 2 * D, c->adj_off.as<long long>());
   stage_end(c);
   c->adj_valid = true;
@@ -1093,24 +1077,37 @@ void bs_size_tables(amg_ctx* c) {
   c->edge_slots = 1024;
 }
 
-static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min_edge_cov, bool* fused);
-
-extern "C" int amg_build(amg_ctx* c, int32_t k) {
-  bool fused = false;
-  return build_impl(c, k, 0, 0, &fused);
+BuildSwitches read_build_switches() {
+  BuildSwitches sw;
+  auto is_zero = [](const char* v) { return v && atoi(v) == 0; };
+  if (const char* e = getenv("AMG_X_HEAD_TILES")) sw.head_tiles_set = true, sw.head_tiles = atoll(e);
+  if (const char* e = getenv("AMG_CLAIM_SHARDS")) sw.claim_shards = atoi(e) != 0;
+  sw.tight_bits = getenv("AMG_X_TIGHT_BITS") != nullptr;
+  if (const char* e = getenv("AMG_KEY_MODE")) sw.key_fp = e[0] == 'f';
+  sw.node_buckets = !is_zero(getenv("AMG_NODE_BUCKETS"));
+  sw.generic_k = getenv("AMG_X_GENERIC_K") != nullptr;
+  sw.rank_sort = getenv("AMG_X_RANK_SORT") != nullptr;
+  if (const char* e = getenv("AMG_EDGE_LONE")) sw.edge_lone = atoi(e) != 0;
+  sw.edge_home = !is_zero(getenv("AMG_EDGE_HOME"));
+  sw.no_derive = getenv("AMG_NO_DERIVE") != nullptr;
+  if (const char* e = getenv("AMG_TEST_WEAK_FP")) sw.weak_fp = atoi(e);
+  if (const char* e = getenv("AMG_COUNT_INLINE")) sw.count_inline = e[0] == '1';
+  return sw;
 }
 
-// GeneMerGraph.__init__ followed by filter_graph(min_node_cov, min_edge_cov) (graph_utils.py:147-149 — what every
-// cleaning iteration does with a freshly built graph).  On the exact-key path the filter is applied ON THE WAY:
-// nodes below the threshold never get an id, an array entry or an edge (an uncorrected graph is ~99 % such
-// nodes), their windows read None and their reads are queued for correction — the state a caller of
-// amg_build + amg_filter finds, except that ids number the survivors only (first-seen order among them).
-// Elsewhere (fingerprint keys) it IS amg_build + amg_filter.
-extern "C" int amg_build_filtered(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min_edge_cov) {
-  bool fused = false;
-  const int r = build_impl(c, k, min_node_cov < 1 ? 1 : min_node_cov, min_edge_cov < 1 ? 1 : min_edge_cov, &fused);
-  if (r != AMG_OK || fused) return r;
-  return amg_filter(c, min_node_cov, min_edge_cov);
+// what the next attempt changes after a table pass returned AMG_E_OVERFLOW for `cause`
+int grow_after_overflow(amg_ctx* c, Overflow cause) {
+  ++c->retries;
+  if (cause == OV_NODE_TABLE) {
+    if (c->node_slots >= (1ll << 30)) return amg_fail(AMG_E_OVERFLOW, "node table at maximum size");
+    c->node_slots = c->node_slots * 4 > (1ll << 30) ? (1ll << 30) : c->node_slots * 4;
+  } else if (cause == OV_EDGE_TABLE) {
+    c->edge_slots *= 4;
+  } else {
+    c->seed = c->seed * 6364136223846793005ull + 1442695040888963407ull;  // new fingerprint
+    if (c->weak_fp_builds > 0) --c->weak_fp_builds;
+  }
+  return AMG_OK;
 }
 
 static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min_edge_cov, bool* fused) {
@@ -1120,9 +1117,10 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
   if (c->two_v <= 0) return amg_fail(AMG_E_STATE, "amg_set_reads first");
   HIPCHK(hipSetDevice(c->device));
   stages_reset(c);
+  c->sw = read_build_switches();
   // the reads are what the last correction left of the reads of the graph still held, nothing re-threaded: that graph's
   // live part IS the graph to build (amg_derive.hip; AMG_NO_DERIVE=1: A/B + test switch)
-  const bool derive = c->derive_ready && k == c->k && !c->dist_mode && !getenv("AMG_NO_DERIVE");
+  const bool derive = c->derive_ready && k == c->k && !c->dist_mode && !c->sw.no_derive;
   c->derive_ready = c->dist_candidate = false;
   c->derived = false;
   c->built = false;
@@ -1143,21 +1141,15 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
     if (c->hint_bound_k == k) c->node_hint = c->hint_bound > 256 ? c->hint_bound : 256;
     c->hint_bound = 0;
   }
-  {
-    // test hook: the first AMG_TEST_WEAK_FP attempts use a 12-bit fingerprint, which is
-    // certain to collide; the exact verification must catch it and the retry must succeed
-    const char* e = getenv("AMG_TEST_WEAK_FP");
-    c->weak_fp_builds = e ? atoi(e) : 0;
-  }
-  {
-    const char* e = getenv("AMG_COUNT_INLINE");  // A/B switch: 1 = one global atomic per window
-    c->count_inline = e && e[0] == '1';
-  }
+  // test hook: the first AMG_TEST_WEAK_FP attempts use a 12-bit fingerprint, which is
+  // certain to collide; the exact verification must catch it and the retry must succeed
+  c->weak_fp_builds = c->sw.weak_fp;
+  c->count_inline = c->sw.count_inline;  // A/B switch: 1 = one global atomic per window
   bs_size_tables(c);
   c->exact_keys = false;
-  const bool exact = bx_applicable(c, k);  // tuple fits the slot: exact keys + claim ids
+  const bool exact = bx_applicable(c, k);  // 16-byte slots: exact tuple keys or verified 94-bit fingerprints, claim ids
   for (int attempt = 0; attempt < 12; ++attempt) {
-    int which = 0;
+    Overflow which = OV_NONE;
     int r;
     if (exact && min_node_cov > 0) {
       r = bx_nodes_filtered(c, k, min_node_cov, &which);
@@ -1181,19 +1173,28 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
       c->node_hint = seen > 256 ? seen : 256;
       return AMG_OK;
     }
-    if (r != AMG_E_OVERFLOW || which == 0) return r;
-    ++c->retries;
-    if (which == 1) {
-      if (c->node_slots >= (1ll << 30)) return amg_fail(AMG_E_OVERFLOW, "node table at maximum size");
-      c->node_slots = c->node_slots * 4 > (1ll << 30) ? (1ll << 30) : c->node_slots * 4;
-    } else if (which == 2) {
-      c->edge_slots *= 4;
-    } else {
-      c->seed = c->seed * 6364136223846793005ull + 1442695040888963407ull;  // new fingerprint
-      if (c->weak_fp_builds > 0) --c->weak_fp_builds;
-    }
+    if (r != AMG_E_OVERFLOW || which == OV_NONE) return r;
+    AMGCHK(grow_after_overflow(c, which));
   }
   return amg_fail(AMG_E_OVERFLOW, "build did not converge after 12 attempts");
+}
+
+extern "C" int amg_build(amg_ctx* c, int32_t k) {
+  bool fused = false;
+  return build_impl(c, k, 0, 0, &fused);
+}
+
+// GeneMerGraph.__init__ followed by filter_graph(min_node_cov, min_edge_cov) (graph_utils.py:147-149 — what every
+// cleaning iteration does with a freshly built graph).  On the exact-key path the filter is applied ON THE WAY:
+// nodes below the threshold never get an id, an array entry or an edge (an uncorrected graph is ~99 % such
+// nodes), their windows read None and their reads are queued for correction — the state a caller of
+// amg_build + amg_filter finds, except that ids number the survivors only (first-seen order among them).
+// Elsewhere (fingerprint keys) it IS amg_build + amg_filter.
+extern "C" int amg_build_filtered(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min_edge_cov) {
+  bool fused = false;
+  const int r = build_impl(c, k, min_node_cov < 1 ? 1 : min_node_cov, min_edge_cov < 1 ? 1 : min_edge_cov, &fused);
+  if (r != AMG_OK || fused) return r;
+  return amg_filter(c, min_node_cov, min_edge_cov);
 }
 
 // ------------------------------------------------------------------ several k over one read set

@@ -1,13 +1,16 @@
-// amg_build_x.hip — the single-GPU build with EXACT keys and claim ids.
+// amg_build_x.hip — the single-GPU build in 16-byte slots with claim ids: EXACT tuple keys, or verified 94-bit
+// fingerprints of the tuple in the same slots.
 //
-// Same result as the fingerprint path of amg_build.hip (GeneMerGraph.__init__, reference
-// construct_graph.py:31-102), different bookkeeping, used whenever the canonical k-tuple
-// fits 94 bits (k * ceil(log2(2V)) <= 94: k = 3 for any vocabulary, k = 5 up to 2^18 genes):
+// Same result as the 32-byte fingerprint path of amg_build.hip (GeneMerGraph.__init__, reference construct_graph.py:31-102),
+// different bookkeeping.  The canonical k-tuple itself is the key whenever it fits 94 bits (k * ceil(log2(2V)) <= 94:
+// k = 3 for any vocabulary, k = 5 up to 2^18 genes); a longer tuple is keyed by its 94-bit fingerprint and every window
+// is verified against its key's first occurrence (next section).  The 32-byte path is still taken for 2^29 tokens and
+// more, for a merged (multi-GPU) build whose tuple does not fit, with AMG_KEY_MODE=fp or AMG_COUNT_INLINE, and for a
+// tuple that would fit while the weak-fingerprint hook (AMG_TEST_WEAK_FP) is set: bx_applicable, bx_fits, bx_tuple_fits.
 //
 //   * a node slot is 16 bytes: w1 = low 63 bits of the packed tuple (+ a set bit 0), w2 =
 //     {remaining tuple bits + a set bit, where the creating window was, claim id + 1} (struct
-//     XW2).  The tuple itself is the key, so no fingerprint verification pass is needed and one
-//     16-byte (plain, L2-served) load per probe decides it; see x_upsert for when a cached view
+//     XW2).  One 16-byte (plain, L2-served) load per probe decides it; see x_upsert for when a cached view
 //     may be trusted.
 //   * the thread that creates a slot gives it a CLAIM id: creators of a block are counted
 //     with a block scan, one atomicAdd per block reserves the ids, the id is published in the
@@ -780,18 +783,13 @@ __global__ void k_x_gather_pairs(const unsigned int* __restrict__ first_sorted,
 #define X_CTRS (F_SHARDS + 1)  // counters of a plain pass: F_SHARDS shards + the first tiles'
 
 // ------------------------------------------------------------------ host side
-#define blocks_for nblk  // (amg_internal.h)
-
-static const unsigned int kProbeLimitX = 1024;
-
 // tiles of the head launch of a table pass (0: none: small inputs): a few coverages of a genome of at most
 // two_v / 2 genes, never more than 1/16 of the tiles.  Every build of a large input gets one, rebuilds with few keys
 // included: the keys that almost every later window hits then hold the lowest claims in stream order, which is what
 // the counting sweeps and the rank bitmaps like (measured on the cleaning sweep: 8.8 -> 8.5 ms against head launches
 // for first builds only; 48 / 64 / 96 / 128 / 156 / 256 / 512 tiles: 9.27 / 9.02 / 8.69 / 8.62 / 8.46 / 8.70 / 8.84 ms).
 static long long head_tiles(const amg_ctx* c, long long n_tiles) {
-  const char* e = getenv("AMG_X_HEAD_TILES");  // A/B switch
-  if (e) return atoll(e) < n_tiles ? atoll(e) : n_tiles;
+  if (c->sw.head_tiles_set) return c->sw.head_tiles < n_tiles ? c->sw.head_tiles : n_tiles;  // A/B switch
   if (n_tiles < 4096) return 0;
   long long h = 4ll * c->two_v / TILE;
   if (h < 64) h = 64;
@@ -808,54 +806,23 @@ static int x_rank_bitmap(amg_ctx* c, const unsigned int* first2, long long n, in
   AMGCHK(c->s1.ensure((size_t)words * sizeof(unsigned int)));
   AMGCHK(c->s5.ensure((size_t)(words + 2) * sizeof(long long)));
   AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
-  if (c->rank_flags_clean != words) {  // (else: zeroed behind the table pass's read-back, read_status)
+  if (c->rank_flags_clean != words) {  // (else: zeroed behind the table pass's read-back, read_pass_status)
     ClearList cl;
     cl.add(c->s0.p, (size_t)words * 32);
     AMGCHK(clear_many(c, cl));
   }
   c->rank_flags_clean = 0;
-  hipLaunchKernelGGL(k_x_rank_setflags, dim3(blocks_for(n, 256)), dim3(256), 0, st, first2, n, shift,
+  hipLaunchKernelGGL(k_x_rank_setflags, dim3(nblk(n, 256)), dim3(256), 0, st, first2, n, shift,
                      c->s0.as<unsigned char>());
   // the flag bytes are folded into the bitmap words by the scan that counts them (one launch, no count array)
   return prim_exscan_flag_words(c, c->s0.as<unsigned char>(), c->s1.as<unsigned int>(), c->s5.as<long long>(), (size_t)words);
 }
 
-// the status words after a table pass; ctrs != nullptr: the pass took its claims from the X_CTRS counters there —
-// their sum replaces host[count_word], the fullest shard's count goes to *most.  rank_filler: the flag bytes of the
-// ranking bitmap that follows (x_rank_bitmap) are zeroed behind the read-back kernel, while the host waits
-static int read_status(amg_ctx* c, unsigned long long* host, const unsigned long long* ctrs = nullptr, int count_word = 0,
-                       unsigned long long* most = nullptr, bool rank_filler = false) {
-  FetchList l;
-  l.add_words(c->status.p, ST_WORDS);
-  if (ctrs)
-    for (int i = 0; i < X_CTRS; ++i) l.add(ctrs + (size_t)i * F_CTR_STRIDE);
-  unsigned long long v[ST_WORDS + X_CTRS];
-  ClearList fill;
-  const long long words = (c->n_tokens >> 5) + 2;
-  if (rank_filler) {
-    AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
-    fill.add(c->s0.p, (size_t)words * 32);
-  }
-  AMGCHK(fetch(c, l, v, rank_filler ? &fill : nullptr));
-  if (rank_filler) c->rank_flags_clean = words;
-  for (int i = 0; i < ST_WORDS; ++i) host[i] = v[i];
-  if (ctrs) {
-    unsigned long long sum = 0, mx = 0;
-    for (int i = 0; i < X_CTRS; ++i) {
-      sum += v[ST_WORDS + i];
-      if (i < (int)F_SHARDS && v[ST_WORDS + i] > mx) mx = v[ST_WORDS + i];
-    }
-    host[count_word] = sum;
-    if (most) *most = mx;
-  }
-  return AMG_OK;
-}
-
 // claims from shard counters (XShard) for the inputs that get a head launch (4 M tokens and more: below that one
 // counter serves a pass's workgroups in the time the pass takes anyway); AMG_CLAIM_SHARDS = 0 / 1: never / always
 // (A/B + test switch)
-static bool shard_claims(long long n_tiles) {
-  if (const char* e = getenv("AMG_CLAIM_SHARDS")) return atoi(e) != 0 && n_tiles > 0;
+static bool shard_claims(const amg_ctx* c, long long n_tiles) {
+  if (c->sw.claim_shards >= 0) return c->sw.claim_shards != 0 && n_tiles > 0;
   return n_tiles >= 4096;
 }
 // a shard's share of `bound` claims: an even split, a quarter of slack, what one workgroup creates in one go; whole chunks
@@ -868,21 +835,100 @@ static unsigned int shard_share(long long bound) {
 // as many after it.  A genome key the head launch has not seen (a dozen of 20 k on cfg 3) is created by one of the
 // next tiles; from a shard counter its claim would lie far above the ids the counting sweeps keep in LDS, and its
 // thousands of occurrences would each be a global atomic on one word (measured: 8 k such windows, +55 us per count).
-static long long dense_tiles(const amg_ctx* c, long long n_tiles) {
-  const long long d = 4 * head_tiles(c, n_tiles);
+static long long dense_tiles(long long head, long long n_tiles) {
+  const long long d = 4 * head;
   return d < n_tiles ? d : n_tiles;
 }
-// claim ids in use lie below this when the fullest shard handed out `most` (head_cap ids in front: the first tiles')
-static long long shard_space(unsigned long long most, long long head_cap, size_t max_claims) {
-  const long long s = head_cap + (long long)((most + X_CHUNK - 1) / X_CHUNK) * (long long)(X_CHUNK * F_SHARDS);
-  return s < (long long)max_claims ? s : (long long)max_claims;
+
+// The claim plan of one table pass (nodes or edge classes): where its claim ids come from and how many there can be.
+struct PassPlan {
+  long long n_tiles;
+  bool plain;      // the caller is the plain build: counting / ranking follow the read-back directly, nobody else writes s0
+  bool sharded;    // claims from the shard counters (then the ids in use have holes: space())
+  unsigned int cap;          // claims per counter
+  long long head;            // tiles of the head launch (0: none)
+  long long head_cap;        // ids of the first tiles
+  size_t max_claims;         // capacity the per-claim arrays need
+  unsigned long long* ctrs;  // the pass's X_CTRS counters; nullptr: one counter in the status words
+
+  void clear_with(ClearList& cl) const { if (ctrs) cl.add(ctrs, X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long)); }
+  // claim ids in use lie below this when `n` were handed out, the fullest shard's `most` (head_cap ids in front)
+  long long space(long long n, unsigned long long most) const {
+    if (!ctrs) return n;
+    const long long s = head_cap + (long long)((most + X_CHUNK - 1) / X_CHUNK) * (long long)(X_CHUNK * F_SHARDS);
+    return s < (long long)max_claims ? s : (long long)max_claims;
+  }
+};
+// sharded, rank_follows: as bx_nodes_upsert's; half: which half of f_ctrs (0 nodes, 1 edge classes)
+static int plan_pass(amg_ctx* c, long long n_tiles, long long claim_bound, bool sharded, bool rank_follows, int half,
+                     PassPlan* p) {
+  p->n_tiles = n_tiles;
+  p->plain = sharded && rank_follows;
+  c->rank_flags_clean = 0;
+  p->sharded = sharded && shard_claims(c, n_tiles);
+  p->head = n_tiles > 0 ? head_tiles(c, n_tiles) : 0;
+  p->cap = p->sharded ? shard_share(claim_bound) : (unsigned int)claim_bound;
+  p->head_cap = p->sharded ? dense_tiles(p->head, n_tiles) * TILE : 0;
+  p->max_claims = p->sharded ? (size_t)p->head_cap + (size_t)p->cap * F_SHARDS + 1 : (size_t)claim_bound;
+  if (p->sharded) AMGCHK(c->f_ctrs.ensure(2 * X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long)));
+  p->ctrs = p->sharded ? c->f_ctrs.as<unsigned long long>() + (size_t)half * X_CTRS * F_CTR_STRIDE : nullptr;
+  return AMG_OK;
+}
+
+// The launches of a table pass: the head launch over the first p.head tiles as stage NAME "_head" (a stage of its own),
+// then the main launch over the rest as stage NAME.  launch(head, first tile, tiles) does the hipLaunchKernelGGL.  The
+// stage is the kernels alone: its time is what bench.py prices against the roofline.  (Names are kept as pointers.)
+#define LAUNCH_HEAD_AND_MAIN(c, p, NAME, ...) launch_head_and_main(c, p, NAME, NAME "_head", __VA_ARGS__)
+template <class Launch>
+static void launch_head_and_main(amg_ctx* c, const PassPlan& p, const char* name, const char* name_head, Launch launch) {
+  stage_begin(c, p.head > 0 ? name_head : name);
+  for (int part = 0; part < 2; ++part) {
+    const long long lo = part == 0 ? 0 : p.head, cnt = part == 0 ? p.head : p.n_tiles - p.head;
+    if (cnt <= 0) continue;  // (no tiles: no launch)
+    if (part == 1 && p.head > 0) {
+      stage_end(c);
+      stage_begin(c, name);
+    }
+    launch(part == 0, (unsigned int)lo, (unsigned int)cnt);
+  }
+  stage_end(c);
+}
+
+// the status words after a table pass: with shard counters (p.ctrs) their sum replaces host[count_word], the fullest
+// shard's count goes to *most.  p.plain: the flag bytes of the ranking bitmap that follows (x_rank_bitmap) are zeroed
+// behind the read-back kernel, while the host waits
+static int read_pass_status(amg_ctx* c, const PassPlan& p, int count_word,
+                            unsigned long long* host /*[ST_WORDS + X_CTRS]*/, unsigned long long* most) {
+  FetchList l;
+  l.add_words(c->status.p, ST_WORDS);
+  if (p.ctrs)
+    for (int i = 0; i < X_CTRS; ++i) l.add(p.ctrs + (size_t)i * F_CTR_STRIDE);
+  unsigned long long* v = host;
+  ClearList fill;
+  const long long words = (c->n_tokens >> 5) + 2;
+  if (p.plain) {
+    AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
+    fill.add(c->s0.p, (size_t)words * 32);
+  }
+  AMGCHK(fetch(c, l, v, p.plain ? &fill : nullptr));
+  if (p.plain) c->rank_flags_clean = words;
+  *most = 0;
+  if (p.ctrs) {
+    unsigned long long sum = 0;
+    for (int i = 0; i < X_CTRS; ++i) {
+      sum += v[ST_WORDS + i];
+      if (i < (int)F_SHARDS && v[ST_WORDS + i] > *most) *most = v[ST_WORDS + i];
+    }
+    host[count_word] = sum;
+  }
+  return AMG_OK;
 }
 
 // bits per token of the packed tuple: 16 whenever that fits (constant shifts in the kernels); AMG_X_TIGHT_BITS=1:
 // as few as the vocabulary needs (test switch: the kernels' general packing, which large vocabularies take)
 int bx_bits(const amg_ctx* c, int k) {
   const int need = ilog2_ceil((uint64_t)(c->two_v > 2 ? c->two_v : 2));
-  if (need <= 16 && (long long)k * 16 <= 94 && !getenv("AMG_X_TIGHT_BITS")) return 16;
+  if (need <= 16 && (long long)k * 16 <= 94 && !c->sw.tight_bits) return 16;
   return need;
 }
 
@@ -891,187 +937,136 @@ bool bx_applicable(const amg_ctx* c, int k) {
   return bx_fits(c, k);
 }
 
-// the tuple fits the slot and first-seen fits 32 bits (per shard in a merged build)
-// the canonical tuple itself fits the 94 key bits of a slot
+// 16-byte slots may be used: 32-bit first-seen ((token << 3) | orientation, per shard in a merged build), no AMG_KEY_MODE=fp
+static bool x_slots_allowed(const amg_ctx* c) { return !c->sw.key_fp && c->n_tokens < (1ll << 29); }
+
+// the canonical tuple itself fits the 94 key bits of a slot (never under the weak-fingerprint hook: the 32-byte path runs)
 bool bx_tuple_fits(const amg_ctx* c, int k) {
-  if (c->weak_fp_builds > 0) return false;
-  const char* e = getenv("AMG_KEY_MODE");  // A/B + test switch: "fp" forces the 32-byte fingerprint path
-  if (e && e[0] == 'f') return false;
-  if ((long long)k * bx_bits(c, k) > 94) return false;
-  if (c->n_tokens >= (1ll << 29)) return false;  // 32-bit first-seen: (token << 3) | orientation
-  return true;
+  return x_slots_allowed(c) && c->weak_fp_builds <= 0 && (long long)k * bx_bits(c, k) <= 94;
 }
 
-// the 16-byte-slot build applies: the tuple fits, or its 94-bit fingerprint is the key (x_fp94)
+// the 16-byte-slot build applies: the tuple fits, or it does not and its 94-bit fingerprint is the key (x_fp94)
 bool bx_fits(const amg_ctx* c, int k) {
-  if (bx_tuple_fits(c, k)) return true;
-  const char* e = getenv("AMG_KEY_MODE");
-  if (e && e[0] == 'f') return false;
-  if (c->n_tokens >= (1ll << 29)) return false;
-  // (a tuple that WOULD fit, with the weak-fingerprint test hook set, keeps exercising the 32-byte path)
-  return (long long)k * bx_bits(c, k) > 94;
+  return bx_tuple_fits(c, k) || (x_slots_allowed(c) && (long long)k * bx_bits(c, k) > 94);
 }
 
-// windows -> node table, claim ids, node ids, node arrays.  AMG_E_OVERFLOW + *which = 1: table full
-int bx_nodes(amg_ctx* c, int k, int* which) {
+// windows -> node table, claim ids, node ids, node arrays.  AMG_E_OVERFLOW + *which = OV_NODE_TABLE: table full
+int bx_nodes(amg_ctx* c, int k, Overflow* which) {
   AMGCHK(bx_nodes_upsert(c, k, which, true));
   return bx_nodes_rank(c);
 }
 
+// The compile-time node kernels, ONE table for k_nodes_m and k_nodes_v: (b16, k in {3, 5, 7}, two) -> <TWO, K, B16>
+#define NODE_KERNEL(KERN, HEAD, b16, k, two)                                                    \
+  ((b16) && (k) == 3   ? KERN<false, 3, true, HEAD>                                             \
+   : (b16) && (k) == 5 ? KERN<true, 5, true, HEAD>                                              \
+   : (k) == 3          ? ((two) ? KERN<true, 3, false, HEAD> : KERN<false, 3, false, HEAD>)     \
+   : (k) == 5          ? ((two) ? KERN<true, 5, false, HEAD> : KERN<false, 5, false, HEAD>)     \
+                       : ((two) ? KERN<true, 7, false, HEAD> : KERN<false, 7, false, HEAD>))
+
 // the table pass alone: claims 0 .. n_local_nodes-1 with their first-seen / slot arrays
 // sharded: claim ids may come from shard counters (then x_nspace > n_nodes: ids nobody took in between)
 // rank_follows: the caller ranks the claims next (x_rank_bitmap): its flag bytes are zeroed behind the status read-back
-int bx_nodes_upsert(amg_ctx* c, int k, int* which, bool sharded, bool rank_follows) {
-  *which = 0;
+int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded, bool rank_follows) {
+  *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens;
-  unsigned long long hs[ST_WORDS];
   c->exact_keys = true;
   c->packed_nodes = false;
   c->x_bits = bx_bits(c, k);
   c->x_fp = (long long)k * c->x_bits > 94;  // the tuple does not fit the slot: its 94-bit fingerprint is the key (x_fp94)
+  c->x_two = c->x_fp || (long long)k * c->x_bits > 63;
+  c->x_kbits = c->x_fp ? 0 : c->x_bits;
   const long long n_tiles = (T + TILE - 1) / TILE;
+  const bool compiled_k = !c->sw.generic_k && !c->x_fp && (k == 3 || k == 5 || k == 7);  // (AMG_X_GENERIC_K: A/B switch)
 
-  // bucket region of the node table (k_nodes_m): one 8-slot line per gene rank in front of the hashed slots, for the
+  // ---- plan.  Bucket region of the node table (k_nodes_m): one 8-slot line per gene rank in front of the hashed slots, for the
   // gene-mer sizes that have a compile-time kernel; AMG_NODE_BUCKETS=0: hashed slots only (k_nodes_v; A/B switch)
-  const char* nb = getenv("AMG_NODE_BUCKETS");
-  const bool buckets = !(nb && atoi(nb) == 0) && !getenv("AMG_X_GENERIC_K") && !c->x_fp &&
-                       (k == 3 || k == 5 || k == 7) && n_tiles > 0;
+  const bool buckets = c->sw.node_buckets && compiled_k && n_tiles > 0;
   const size_t home_n = buckets ? (size_t)4 * (size_t)c->two_v : 0;  // 8 slots x (two_v / 2) gene ranks
   const size_t tab_slots = (size_t)c->node_slots + home_n;
-  const long long claim_bound = ((long long)tab_slots < T ? (long long)tab_slots : T) + 1;
-  const bool plain = sharded && rank_follows;  // the caller is the plain build: ranking follows the read-back directly
-  c->rank_flags_clean = 0;
-  sharded = sharded && shard_claims(n_tiles);
-  const unsigned int cap = sharded ? shard_share(claim_bound) : (unsigned int)claim_bound;  // per counter
-  const long long head_cap = sharded ? dense_tiles(c, n_tiles) * TILE : 0;                  // ids of the first tiles
-  const size_t max_claims = sharded ? (size_t)head_cap + (size_t)cap * F_SHARDS + 1 : (size_t)claim_bound;
-  unsigned long long* ctrs = nullptr;
-  if (sharded) {
-    AMGCHK(c->f_ctrs.ensure(2 * X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long)));
-    ctrs = c->f_ctrs.as<unsigned long long>();
-  }
+  PassPlan p;
+  AMGCHK(plan_pass(c, n_tiles, ((long long)tab_slots < T ? (long long)tab_slots : T) + 1, sharded, rank_follows, 0, &p));
+  // ---- ensure
   AMGCHK(c->tok_slot.ensure((size_t)(T + 8) * sizeof(int)));
   AMGCHK(c->tok_node.ensure((size_t)(T + 8) * sizeof(int)));
   AMGCHK(c->tok_dir.ensure((size_t)(T + 8)));
   AMGCHK(c->node_tab.ensure(tab_slots * sizeof(Slot16)));
-  AMGCHK(c->x_first.ensure(2 * max_claims * sizeof(unsigned int)));  // {raised by others, creator's} per claim
-  AMGCHK(c->x_slot.ensure(max_claims * sizeof(unsigned int)));
-  AMGCHK(c->x_final.ensure(max_claims * sizeof(int)));
-
-  {  // status words, table, first-seen words and the read-end bitmap are zeroed by ONE launch
+  AMGCHK(c->x_first.ensure(2 * p.max_claims * sizeof(unsigned int)));  // {raised by others, creator's} per claim
+  AMGCHK(c->x_slot.ensure(p.max_claims * sizeof(unsigned int)));
+  AMGCHK(c->x_final.ensure(p.max_claims * sizeof(int)));
+  {  // ---- clear: status words, table, first-seen words and the read-end bitmap are zeroed by ONE launch
     ClearList cl;
     cl.add(c->status.p, ST_WORDS * sizeof(unsigned long long));
     cl.add(c->node_tab.p, tab_slots * sizeof(Slot16));
-    cl.add(c->x_first.p, 2 * max_claims * sizeof(unsigned int));
-    if (ctrs) cl.add(ctrs, X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long));
+    cl.add(c->x_first.p, 2 * p.max_claims * sizeof(unsigned int));
+    p.clear_with(cl);
     AMGCHK(bs_read_stats(c, k, &cl));
   }
-
-  stage_begin(c, (n_tiles > 0 && head_tiles(c, n_tiles) > 0) ? "node_upsert_head" : "node_upsert");
-  if (n_tiles > 0) {
-    const bool two = c->x_fp || (long long)k * c->x_bits > 63;  // tuple spills into w2?
-    if (buckets) {
-      const bool b16 = c->x_bits == 16 && (k == 3 || k == 5);
-      auto kern = k_nodes_m<false, 3, false>;
-      auto kern_head = k_nodes_m<false, 3, false, true>;
-      if (b16 && k == 3) kern = k_nodes_m<false, 3, true>, kern_head = k_nodes_m<false, 3, true, true>;
-      else if (b16 && k == 5) kern = k_nodes_m<true, 5, true>, kern_head = k_nodes_m<true, 5, true, true>;
-      else if (k == 3) kern = two ? k_nodes_m<true, 3, false> : k_nodes_m<false, 3, false>,
-                       kern_head = two ? k_nodes_m<true, 3, false, true> : k_nodes_m<false, 3, false, true>;
-      else if (k == 5) kern = two ? k_nodes_m<true, 5, false> : k_nodes_m<false, 5, false>,
-                       kern_head = two ? k_nodes_m<true, 5, false, true> : k_nodes_m<false, 5, false, true>;
-      else kern = two ? k_nodes_m<true, 7, false> : k_nodes_m<false, 7, false>,
-           kern_head = two ? k_nodes_m<true, 7, false, true> : k_nodes_m<false, 7, false, true>;
-      const long long head = head_tiles(c, n_tiles);  // (see below: the genome's keys get the lowest claims — and the first slots of their lines)
-      for (int part = 0; part < 2; ++part) {
-        const long long lo = part == 0 ? 0 : head, cnt = part == 0 ? head : n_tiles - head;
-        if (cnt <= 0) continue;
-        if (part == 1 && head > 0) {  // the head launch is a stage of its own
-          stage_end(c);
-          stage_begin(c, "node_upsert");
-        }
-        hipLaunchKernelGGL(part == 0 ? kern_head : kern, dim3((unsigned)cnt), dim3(TILE_THREADS), 0, st, c->tokens.as<int>(),
-                           c->bnd_bits.as<unsigned int>(), T, c->two_v, c->x_bits, c->node_tab.as<Slot16>(),
-                           (unsigned int)(c->node_slots - 1), kProbeLimitX, c->tok_slot.as<int>(),
-                           c->tok_dir.as<signed char>(), c->status.as<unsigned long long>(),
-                           c->x_first.as<unsigned int>(), c->x_slot.as<unsigned int>(), cap,
-                           xw2_for(max_claims, T), (unsigned int)lo, (unsigned int)home_n, ctrs, (unsigned int)head_cap);
-      }
-    } else {
-      const bool b16 = c->x_bits == 16 && (k == 3 || k == 5);
-      auto kern = two ? k_nodes_v<true, 0, false> : k_nodes_v<false, 0, false>;
-      auto kern_head = two ? k_nodes_v<true, 0, false, true> : k_nodes_v<false, 0, false, true>;
-      if (!getenv("AMG_X_GENERIC_K") && !c->x_fp) {  // A/B switch
-        if (b16 && k == 3) kern = k_nodes_v<false, 3, true>, kern_head = k_nodes_v<false, 3, true, true>;
-        else if (b16 && k == 5) kern = k_nodes_v<true, 5, true>, kern_head = k_nodes_v<true, 5, true, true>;
-        else if (k == 3) kern = two ? k_nodes_v<true, 3, false> : k_nodes_v<false, 3, false>,
-                         kern_head = two ? k_nodes_v<true, 3, false, true> : k_nodes_v<false, 3, false, true>;
-        else if (k == 5) kern = two ? k_nodes_v<true, 5, false> : k_nodes_v<false, 5, false>,
-                         kern_head = two ? k_nodes_v<true, 5, false, true> : k_nodes_v<false, 5, false, true>;
-        else if (k == 7) kern = two ? k_nodes_v<true, 7, false> : k_nodes_v<false, 7, false>,
-                         kern_head = two ? k_nodes_v<true, 7, false, true> : k_nodes_v<false, 7, false, true>;
-      }
-      // Claim ids follow the order in which the ~2000 concurrently running tiles create keys: with many creations
-      // per tile (a first build: one window in ten) the genome's keys, which almost every later window hits,
-      // get claims scattered over the first few hundred thousand, and whoever counts by claim (k_count_ids, one
-      // LDS range of 32 k ids per sweep) needs several sweeps.  A short head launch over the first few genome
-      // coverages creates them first: their claims are then the lowest.
-      const long long head = head_tiles(c, n_tiles);
-      for (int part = 0; part < 2; ++part) {
-        const long long lo = part == 0 ? 0 : head, cnt = part == 0 ? head : n_tiles - head;
-        if (cnt <= 0) continue;
-        if (part == 1 && head > 0) {  // the head launch is a stage of its own
-          stage_end(c);
-          stage_begin(c, "node_upsert");
-        }
-        hipLaunchKernelGGL(part == 0 ? kern_head : kern, dim3((unsigned)cnt), dim3(TILE_THREADS), 0, st, c->tokens.as<int>(),
-                           c->bnd_bits.as<unsigned int>(), T, k, c->two_v, c->x_fp ? 0 : c->x_bits,
-                           c->node_tab.as<Slot16>(), (unsigned int)(c->node_slots - 1), kProbeLimitX,
-                           c->tok_slot.as<int>(), c->tok_dir.as<signed char>(),
-                           c->status.as<unsigned long long>(), c->x_first.as<unsigned int>(),
-                           c->x_slot.as<unsigned int>(), cap, xw2_for(max_claims, T), (unsigned int)lo, ctrs,
-                           (unsigned int)head_cap, (unsigned long long)c->seed, c->weak_fp_builds > 0 ? 1 : 0);
-      }
-    }
+  // ---- launch
+  // Claim ids follow the order in which the ~2000 concurrently running tiles create keys: with many creations
+  // per tile (a first build: one window in ten) the genome's keys, which almost every later window hits,
+  // get claims scattered over the first few hundred thousand, and whoever counts by claim (k_count_ids, one
+  // LDS range of 32 k ids per sweep) needs several sweeps.  A short head launch over the first few genome
+  // coverages creates them first: their claims are then the lowest (and, with buckets, theirs are the first slots
+  // of their lines).
+  const bool b16 = c->x_bits == 16 && (k == 3 || k == 5);
+  const XW2 xf = xw2_for(p.max_claims, T);
+  if (buckets) {
+    auto kern = NODE_KERNEL(k_nodes_m, false, b16, k, c->x_two), kern_head = NODE_KERNEL(k_nodes_m, true, b16, k, c->x_two);
+    LAUNCH_HEAD_AND_MAIN(c, p, "node_upsert", [&](bool head, unsigned int lo, unsigned int cnt) {
+      hipLaunchKernelGGL(head ? kern_head : kern, dim3(cnt), dim3(TILE_THREADS), 0, st, c->tokens.as<int>(),
+                         c->bnd_bits.as<unsigned int>(), T, c->two_v, c->x_bits, c->node_tab.as<Slot16>(),
+                         (unsigned int)(c->node_slots - 1), kProbeLimit, c->tok_slot.as<int>(),
+                         c->tok_dir.as<signed char>(), c->status.as<unsigned long long>(),
+                         c->x_first.as<unsigned int>(), c->x_slot.as<unsigned int>(), p.cap, xf, lo,
+                         (unsigned int)home_n, p.ctrs, (unsigned int)p.head_cap);
+    });
+  } else {
+    auto kern = c->x_two ? k_nodes_v<true, 0, false> : k_nodes_v<false, 0, false>;  // k at run time
+    auto kern_head = c->x_two ? k_nodes_v<true, 0, false, true> : k_nodes_v<false, 0, false, true>;
+    if (compiled_k)
+      kern = NODE_KERNEL(k_nodes_v, false, b16, k, c->x_two), kern_head = NODE_KERNEL(k_nodes_v, true, b16, k, c->x_two);
+    LAUNCH_HEAD_AND_MAIN(c, p, "node_upsert", [&](bool head, unsigned int lo, unsigned int cnt) {
+      hipLaunchKernelGGL(head ? kern_head : kern, dim3(cnt), dim3(TILE_THREADS), 0, st, c->tokens.as<int>(),
+                         c->bnd_bits.as<unsigned int>(), T, k, c->two_v, c->x_kbits, c->node_tab.as<Slot16>(),
+                         (unsigned int)(c->node_slots - 1), kProbeLimit, c->tok_slot.as<int>(),
+                         c->tok_dir.as<signed char>(), c->status.as<unsigned long long>(),
+                         c->x_first.as<unsigned int>(), c->x_slot.as<unsigned int>(), p.cap, xf, lo, p.ctrs,
+                         (unsigned int)p.head_cap, (unsigned long long)c->seed, c->weak_fp_builds > 0 ? 1 : 0);
+    });
   }
-  stage_end(c);  // the stage is the kernel alone: its time is what bench.py prices against the roofline
   if (c->x_fp && n_tiles > 0) {
     // fingerprint keys: every window's tuple against its claim's first occurrence; a mismatch raises ST_COLLISION,
-    // which the next read-back of the status words reports (bx_edges_upsert / bx_nodes_filtered): which = 3
+    // which the next read-back of the status words reports (here / bx_nodes_filtered): OV_COLLISION
     stage_begin(c, "node_verify");
-    hipLaunchKernelGGL(k_x_verify_fp, dim3(blocks_for(T, 256)), dim3(256), 0, st, c->tokens.as<int>(), T, k, c->two_v - 1,
+    hipLaunchKernelGGL(k_x_verify_fp, dim3(nblk(T, 256)), dim3(256), 0, st, c->tokens.as<int>(), T, k, c->two_v - 1,
                        c->tok_slot.as<int>(), c->tok_dir.as<signed char>(), c->x_first.as<unsigned int>(),
                        c->status.as<unsigned long long>());
     stage_end(c);
   }
-  unsigned long long most = 0;
-  AMGCHK(read_status(c, hs, ctrs, ST_NODE_INSERTS, &most, plain));
+  // ---- read back, decode
+  unsigned long long hs[ST_WORDS + X_CTRS], most;
+  AMGCHK(read_pass_status(c, p, ST_NODE_INSERTS, hs, &most));
   if (hs[ST_BADINPUT])
     return amg_fail(AMG_E_ARG, hs[ST_BADINPUT] == 1 ? "read_offsets must start at 0, never decrease and end at the token count"
                                                     : "a token lies outside [0, two_v)");
   if (hs[ST_PALINDROME])
     return amg_fail(AMG_E_PALINDROME, "Gene-mer and reverse complement gene-mer are identical");
   if (hs[ST_MISC]) return amg_fail(AMG_E_HIP, "node pass: a claim id was never published");
-  if (hs[ST_COLLISION]) {  // fingerprint keys: k_x_verify_fp found two gene-mers under one key — nothing is built on this table
-    *which = 3;
-    return AMG_E_OVERFLOW;
-  }
-  if (hs[ST_OVERFLOW]) {
-    *which = 1;
-    return AMG_E_OVERFLOW;
-  }
+  if (hs[ST_COLLISION]) return overflowed(which, OV_COLLISION);  // (fingerprint keys: k_x_verify_fp found two gene-mers under one key)
+  if (hs[ST_OVERFLOW]) return overflowed(which, OV_NODE_TABLE);
   c->n_windows = (int64_t)hs[ST_N_WINDOWS];
   c->n_short = (int64_t)hs[ST_N_SHORT];
   c->n_local_nodes = c->n_nodes = (int64_t)hs[ST_NODE_INSERTS];
-  c->x_nspace = ctrs ? shard_space(most, head_cap, max_claims) : c->n_nodes;
-  c->x_max_claims = (int64_t)max_claims;
+  c->x_nspace = p.space(c->n_nodes, most);
+  c->x_max_claims = (int64_t)p.max_claims;
   return AMG_OK;
 }
 
 // node table pass, then only the nodes with coverage >= min_cov are kept: ids, arrays and coverages of the
 // survivors; x_final = -2 for the others
-int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, int* which) {
+int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, Overflow* which) {
   hipStream_t st = c->stream;
   c->filtered_build = true;
   const int r0 = bx_nodes_upsert(c, k, which, true);
@@ -1090,7 +1085,7 @@ int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, int* which) {
   unsigned long long* kept = c->status.as<unsigned long long>() + ST_COMPACT_A;
   HIPCHK(hipMemsetAsync(kept, 0, sizeof(unsigned long long), st));
   if (n > 0)
-    hipLaunchKernelGGL(k_x_drop_claims, dim3(blocks_for(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), n,
+    hipLaunchKernelGGL(k_x_drop_claims, dim3(nblk(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), n,
                        min_cov, c->x_first.as<unsigned int>(), c->x_final.as<int>(), kept,
                        c->x_first_all.as<unsigned int>());
   unsigned long long D = 0;
@@ -1103,15 +1098,14 @@ int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, int* which) {
     D = v[0];
     if (v[1]) {  // two gene-mers share a fingerprint (k_x_verify_fp): the build is repeated with the next seed
       stage_end(c);
-      *which = 3;
-      return AMG_E_OVERFLOW;
+      return overflowed(which, OV_COLLISION);
     }
   }
   stage_end(c);
   c->n_nodes = (int64_t)D;
   AMGCHK(bx_nodes_rank(c));
   if (n > 0 && D > 0)
-    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(blocks_for(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(),
+    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(nblk(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(),
                        c->x_first.as<unsigned int>(), c->x_final.as<int>(), n, c->node_cov.as<unsigned int>(), (int*)nullptr);
   return AMG_OK;
 }
@@ -1129,24 +1123,24 @@ int bx_nodes_rank(amg_ctx* c) {
   AMGCHK(c->s4.ensure((size_t)(D + 1) * sizeof(unsigned int)));
   AMGCHK(bs_alloc_nodes(c, D));
   const long long S = c->x_nspace;  // claim ids in use (== D unless handed out in interleaved shards)
-  if (D > 0 && ((D <= kRankBitmapMax && !getenv("AMG_X_RANK_SORT")) || S != D)) {
+  if (D > 0 && ((D <= kRankBitmapMax && !c->sw.rank_sort) || S != D)) {
     AMGCHK(x_rank_bitmap(c, c->x_first.as<unsigned int>(), S, 1));
-    hipLaunchKernelGGL(k_x_assign_nodes_ranked, dim3(blocks_for(S, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_x_assign_nodes_ranked, dim3(nblk(S, 256)), dim3(256), 0, st,
                        c->x_first.as<unsigned int>(), S,
                        c->s1.as<unsigned int>(), c->s5.as<long long>(), c->node_tab.as<Slot16>(),
-                       c->x_slot.as<unsigned int>(), k, c->x_fp ? 0 : c->x_bits, (c->x_fp || (long long)k * c->x_bits > 63) ? 1 : 0,
+                       c->x_slot.as<unsigned int>(), k, c->x_kbits, c->x_two ? 1 : 0,
                        c->x_final.as<int>(), c->node_tokens.as<int>(),
                        c->node_first.as<long long>(), c->node_alive.as<unsigned char>(), c->tokens.as<int>(), c->two_v - 1);
   } else if (D > 0) {
     c->rank_flags_clean = 0;  // (s0 is about to be reused by whoever comes next: nothing of it is known to be zero)
-    hipLaunchKernelGGL(k_x_sort_keys, dim3(blocks_for(D, 256)), dim3(256), 0, st, c->x_first.as<unsigned int>(),
+    hipLaunchKernelGGL(k_x_sort_keys, dim3(nblk(D, 256)), dim3(256), 0, st, c->x_first.as<unsigned int>(),
                        D, c->s1.as<unsigned int>(),
                        c->s3.as<unsigned int>());
     AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s2.as<unsigned int>(), c->s3.as<unsigned int>(),
                              c->s4.as<unsigned int>(), (size_t)D, ilog2_ceil((uint64_t)T * 2 + 2) + 1));
-    hipLaunchKernelGGL(k_x_assign_nodes, dim3(blocks_for(D, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
+    hipLaunchKernelGGL(k_x_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
                        c->s4.as<unsigned int>(), D, c->node_tab.as<Slot16>(), c->x_slot.as<unsigned int>(),
-                       k, c->x_fp ? 0 : c->x_bits, (c->x_fp || (long long)k * c->x_bits > 63) ? 1 : 0, c->x_final.as<int>(),
+                       k, c->x_kbits, c->x_two ? 1 : 0, c->x_final.as<int>(),
                        c->node_tokens.as<int>(), c->node_first.as<long long>(), c->node_alive.as<unsigned char>(),
                        c->tokens.as<int>(), c->two_v - 1);
   }
@@ -1155,17 +1149,16 @@ int bx_nodes_rank(amg_ctx* c) {
 }
 
 // adjacencies -> edge-class table, claims, pair arrays in first-seen order, coverages.
-// AMG_E_OVERFLOW + *which = 2: edge table full
-int bx_edges(amg_ctx* c, int* which, unsigned int min_edge_cov) {
+// AMG_E_OVERFLOW + *which = OV_EDGE_TABLE: edge table full
+int bx_edges(amg_ctx* c, Overflow* which, unsigned int min_edge_cov) {
   // a plain build counts its nodes BEFORE the edge pass: the nodes of coverage 1 (nine in ten of an uncorrected
   // graph) mark the edge classes that occur once, and those need no table (k_edges_v<.., LONE>)
   bool lone = false;
   if (min_edge_cov == 0) {
-    const char* e = getenv("AMG_EDGE_LONE");  // A/B + test switch: 0 never, 1 whenever the kernel allows it
-    const char* eh = getenv("AMG_EDGE_HOME");
-    const bool can = !(eh && atoi(eh) == 0) && c->n_nodes > 0;
-    // worth its extra words per window where many nodes are single: more than one node per 16 windows
-    lone = can && (e ? atoi(e) != 0 : c->n_nodes * 16 > c->n_tokens);
+    const bool can = c->sw.edge_home && c->n_nodes > 0;
+    // AMG_EDGE_LONE (A/B + test switch): 0 never, 1 whenever the kernel allows it; else where it is
+    // worth its extra words per window: where many nodes are single, more than one node per 16 windows
+    lone = can && (c->sw.edge_lone >= 0 ? c->sw.edge_lone != 0 : c->n_nodes * 16 > c->n_tokens);
     AMGCHK(bx_node_count(c, lone));
   }
   AMGCHK(bx_edges_upsert(c, which, lone, min_edge_cov == 0));
@@ -1183,7 +1176,7 @@ int bx_node_count(amg_ctx* c, bool tag) {
   if (tag) AMGCHK(c->x_ftag.ensure((size_t)(S + 2) * sizeof(int)));
   AMGCHK(count_ids(c, c->tok_slot.as<int>(), T, nullptr, S, c->x_ncnt.as<unsigned int>(), 4));
   if (S > 0 && D > 0)
-    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(blocks_for(S, 256)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(nblk(S, 256)), dim3(256), 0, c->stream,
                        c->x_ncnt.as<unsigned int>(), c->x_first.as<unsigned int>(), c->x_final.as<int>(), S,
                        c->node_cov.as<unsigned int>(), tag ? c->x_ftag.as<int>() : (int*)nullptr);
   stage_end(c);
@@ -1193,15 +1186,13 @@ int bx_node_count(amg_ctx* c, bool tag) {
 // the table pass alone: tok_node from x_final, edge-class claims 0 .. n_local_pairs-1
 // lone: x_ftag marks the nodes of coverage 1 (bx_node_count); their classes bypass the table
 // sharded, rank_follows: as bx_nodes_upsert's
-int bx_edges_upsert(amg_ctx* c, int* which, bool lone, bool sharded, bool rank_follows) {
-  *which = 0;
+int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, bool sharded, bool rank_follows) {
+  *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens, D = c->n_nodes;
   const long long n_tiles = (T + TILE - 1) / TILE;
-  unsigned long long hs[ST_WORDS];
-  // home slots (k_edges_v<.., true>): one per node id in front of the hashed slots; AMG_EDGE_HOME=0: none (A/B switch)
-  const char* eh = getenv("AMG_EDGE_HOME");
-  const long long home_n = (eh && atoi(eh) == 0) ? 0 : ((D + 7) & ~7ll);
+  // ---- plan.  Home slots (k_edges_v<.., true>): one per node id in front of the hashed slots; AMG_EDGE_HOME=0: none (A/B switch)
+  const long long home_n = c->sw.edge_home ? ((D + 7) & ~7ll) : 0;
   // hashed slots: with home slots only the classes that do not join ids n and n + 1 (one in ten on gene-call reads)
   // need one — sized for a quarter of the nodes; an input that needs more overflows once and is rebuilt 4x larger
   const int64_t want_slots = (int64_t)slots_for((uint64_t)(home_n ? D / 4 + 1 : D));
@@ -1209,70 +1200,47 @@ int bx_edges_upsert(amg_ctx* c, int* which, bool lone, bool sharded, bool rank_f
   const size_t tab_slots = (size_t)c->edge_slots + (size_t)home_n;
   if (!home_n) lone = false;
   // claims: at most one per table slot, plus (lone) two classes per single node, never more than the windows
-  long long claim_bound = (long long)tab_slots + (lone ? 2 * D : 0);
-  claim_bound = (claim_bound < T ? claim_bound : T) + 1;
-  const bool plain = sharded && rank_follows;  // the caller is the plain build: counting and ranking follow, nobody else writes s0
-  c->rank_flags_clean = 0;
-  sharded = sharded && shard_claims(n_tiles);
-  const unsigned int cap = sharded ? shard_share(claim_bound) : (unsigned int)claim_bound;  // per counter
-  const long long head_cap = sharded ? dense_tiles(c, n_tiles) * TILE : 0;                  // ids of the first tiles
-  const size_t max_claims = sharded ? (size_t)head_cap + (size_t)cap * F_SHARDS + 1 : (size_t)claim_bound;
-  unsigned long long* ctrs = nullptr;
-  if (sharded) {
-    AMGCHK(c->f_ctrs.ensure(2 * X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long)));
-    ctrs = c->f_ctrs.as<unsigned long long>() + X_CTRS * F_CTR_STRIDE;
-  }
+  const long long claim_bound = (long long)tab_slots + (lone ? 2 * D : 0);
+  PassPlan p;
+  AMGCHK(plan_pass(c, n_tiles, (claim_bound < T ? claim_bound : T) + 1, sharded, rank_follows, 1, &p));
+  // ---- ensure
   AMGCHK(c->tok_pair.ensure((size_t)(T + 8) * sizeof(int)));
-  AMGCHK(c->edge_tab.ensure((tab_slots + (lone ? max_claims : 0)) * sizeof(Slot16)));  // (lone classes: slot = tab_slots + claim)
-  AMGCHK(c->x_efirst.ensure(2 * max_claims * sizeof(unsigned int)));
-  AMGCHK(c->x_eslot.ensure(max_claims * sizeof(unsigned int)));
+  AMGCHK(c->edge_tab.ensure((tab_slots + (lone ? p.max_claims : 0)) * sizeof(Slot16)));  // (lone classes: slot = tab_slots + claim)
+  AMGCHK(c->x_efirst.ensure(2 * p.max_claims * sizeof(unsigned int)));
+  AMGCHK(c->x_eslot.ensure(p.max_claims * sizeof(unsigned int)));
+  // ---- clear
   stage_begin(c, "edge_table_clear");
   {
     ClearList cl;
     cl.add(c->edge_tab.p, tab_slots * sizeof(Slot16));
-    cl.add(c->x_efirst.p, 2 * max_claims * sizeof(unsigned int));
+    cl.add(c->x_efirst.p, 2 * p.max_claims * sizeof(unsigned int));
     cl.add(c->status.as<unsigned long long>() + ST_PAIR_INSERTS, 2 * sizeof(unsigned long long));
-    if (ctrs) cl.add(ctrs, X_CTRS * F_CTR_STRIDE * sizeof(unsigned long long));
+    p.clear_with(cl);
     AMGCHK(clear_many(c, cl));
   }
   stage_end(c);
-  stage_begin(c, (n_tiles > 0 && head_tiles(c, n_tiles) > 0) ? "edge_upsert_head" : "edge_upsert");
-  if (n_tiles > 0) {
-    const long long head = head_tiles(c, n_tiles);  // (see bx_nodes_upsert: the genome's classes get the lowest claims)
-    for (int part = 0; part < 2; ++part) {
-      const long long lo = part == 0 ? 0 : head, cnt = part == 0 ? head : n_tiles - head;
-      if (cnt <= 0) continue;
-      if (part == 1 && head > 0) {  // the head launch is a stage of its own
-        stage_end(c);
-        stage_begin(c, "edge_upsert");
-      }
-      auto kern = lone     ? (part == 0 ? k_edges_v<true, true, true> : k_edges_v<false, true, true>)
-                  : home_n ? (part == 0 ? k_edges_v<true, true> : k_edges_v<false, true>)
-                           : (part == 0 ? k_edges_v<true, false> : k_edges_v<false, false>);
-      hipLaunchKernelGGL(kern, dim3((unsigned)cnt), dim3(TILE_THREADS), 0, st, T, c->tok_slot.as<int>(),
-                         c->tok_dir.as<signed char>(), lone ? c->x_ftag.as<int>() : c->x_final.as<int>(),
-                         c->tok_node.as<int>(), c->edge_tab.as<Slot16>(), (unsigned int)(c->edge_slots - 1), kProbeLimitX,
-                         c->status.as<unsigned long long>(), c->tok_pair.as<int>(),
-                         c->x_efirst.as<unsigned int>(), c->x_eslot.as<unsigned int>(), cap,
-                         xw2_for(max_claims, T), (unsigned int)lo, (unsigned int)home_n, (unsigned int)tab_slots, ctrs,
-                         (unsigned int)head_cap);
-    }
-  }
-  stage_end(c);  // the stage is the kernel alone: its time is what bench.py prices against the roofline
-  unsigned long long most = 0;
-  AMGCHK(read_status(c, hs, ctrs, ST_PAIR_INSERTS, &most, plain));
+  // ---- launch (the head launch: see bx_nodes_upsert — the genome's classes get the lowest claims)
+  const XW2 xf = xw2_for(p.max_claims, T);
+  LAUNCH_HEAD_AND_MAIN(c, p, "edge_upsert", [&](bool head, unsigned int lo, unsigned int cnt) {
+    auto kern = lone     ? (head ? k_edges_v<true, true, true> : k_edges_v<false, true, true>)
+                : home_n ? (head ? k_edges_v<true, true> : k_edges_v<false, true>)
+                         : (head ? k_edges_v<true, false> : k_edges_v<false, false>);
+    hipLaunchKernelGGL(kern, dim3(cnt), dim3(TILE_THREADS), 0, st, T, c->tok_slot.as<int>(),
+                       c->tok_dir.as<signed char>(), lone ? c->x_ftag.as<int>() : c->x_final.as<int>(),
+                       c->tok_node.as<int>(), c->edge_tab.as<Slot16>(), (unsigned int)(c->edge_slots - 1), kProbeLimit,
+                       c->status.as<unsigned long long>(), c->tok_pair.as<int>(),
+                       c->x_efirst.as<unsigned int>(), c->x_eslot.as<unsigned int>(), p.cap, xf, lo,
+                       (unsigned int)home_n, (unsigned int)tab_slots, p.ctrs, (unsigned int)p.head_cap);
+  });
+  // ---- read back, decode
+  unsigned long long hs[ST_WORDS + X_CTRS], most;
+  AMGCHK(read_pass_status(c, p, ST_PAIR_INSERTS, hs, &most));
   if (hs[ST_MISC]) return amg_fail(AMG_E_HIP, "edge pass: a claim id was never published");
-  if (hs[ST_COLLISION]) {  // fingerprint keys: k_x_verify_fp found two gene-mers under one key
-    *which = 3;
-    return AMG_E_OVERFLOW;
-  }
-  if (hs[ST_OVERFLOW]) {
-    *which = 2;
-    return AMG_E_OVERFLOW;
-  }
+  if (hs[ST_COLLISION]) return overflowed(which, OV_COLLISION);  // (fingerprint keys: k_x_verify_fp found two gene-mers under one key)
+  if (hs[ST_OVERFLOW]) return overflowed(which, OV_EDGE_TABLE);
   c->n_local_pairs = c->n_pairs = (int64_t)hs[ST_PAIR_INSERTS];
-  c->x_espace = ctrs ? shard_space(most, head_cap, max_claims) : c->n_pairs;
-  c->x_max_eclaims = (int64_t)max_claims;
+  c->x_espace = p.space(c->n_pairs, most);
+  c->x_max_eclaims = (int64_t)p.max_claims;
   return AMG_OK;
 }
 
@@ -1290,7 +1258,7 @@ int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov, bool nodes_counted) {
     hipStream_t st = c->stream;
     unsigned long long* kept = c->status.as<unsigned long long>() + ST_COMPACT_A;
     HIPCHK(hipMemsetAsync(kept, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_x_drop_claims, dim3(blocks_for(P, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), P,
+    hipLaunchKernelGGL(k_x_drop_claims, dim3(nblk(P, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), P,
                        min_edge_cov, c->x_efirst.as<unsigned int>(), (int*)nullptr, kept, (unsigned int*)nullptr);
     unsigned long long left = 0;
     FetchList l;
@@ -1304,7 +1272,7 @@ int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov, bool nodes_counted) {
 // after bs_finish_from_pairs of a filtered build: the reads the filter touched
 int bx_flag_dead_reads(amg_ctx* c) {
   if (c->n_reads > 0)
-    hipLaunchKernelGGL(k_x_flag_dead_reads, dim3(blocks_for(c->n_reads, FD_READS)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_x_flag_dead_reads, dim3(nblk(c->n_reads, FD_READS)), dim3(256), 0, c->stream,
                        c->tok_node.as<int>(), c->read_off.as<long long>(), c->n_reads, c->read_fix.as<unsigned char>());
   return AMG_OK;
 }
@@ -1322,9 +1290,9 @@ int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal) {
   AMGCHK(c->s3.ensure((size_t)(P + 1) * sizeof(unsigned int)));
   AMGCHK(c->s4.ensure((size_t)(P + 1) * sizeof(unsigned int)));
   const long long S = c->x_espace;
-  if (P > 0 && ((P <= kRankBitmapMax && !getenv("AMG_X_RANK_SORT")) || S != P || efinal)) {
+  if (P > 0 && ((P <= kRankBitmapMax && !c->sw.rank_sort) || S != P || efinal)) {
     AMGCHK(x_rank_bitmap(c, c->x_efirst.as<unsigned int>(), S, 3));
-    hipLaunchKernelGGL(k_x_gather_pairs_ranked, dim3(blocks_for(S, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_x_gather_pairs_ranked, dim3(nblk(S, 256)), dim3(256), 0, st,
                        c->x_efirst.as<unsigned int>(), S,
                        c->s1.as<unsigned int>(), c->s5.as<long long>(), c->edge_tab.as<Slot16>(),
                        c->x_eslot.as<unsigned int>(), c->x_ecnt.as<unsigned int>(),
@@ -1333,12 +1301,12 @@ int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal) {
   } else if (P > 0) {
     c->rank_flags_clean = 0;
     if (efinal) return amg_fail(AMG_E_STATE, "bx_pairs_rank: class ids per claim need the bitmap ranking");
-    hipLaunchKernelGGL(k_x_sort_keys, dim3(blocks_for(P, 256)), dim3(256), 0, st, c->x_efirst.as<unsigned int>(),
+    hipLaunchKernelGGL(k_x_sort_keys, dim3(nblk(P, 256)), dim3(256), 0, st, c->x_efirst.as<unsigned int>(),
                        P, c->s1.as<unsigned int>(),
                        c->s3.as<unsigned int>());
     AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s2.as<unsigned int>(), c->s3.as<unsigned int>(),
                              c->s4.as<unsigned int>(), (size_t)P, ilog2_ceil((uint64_t)T * 8 + 8) + 1));
-    hipLaunchKernelGGL(k_x_gather_pairs, dim3(blocks_for(P, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
+    hipLaunchKernelGGL(k_x_gather_pairs, dim3(nblk(P, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
                        c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot16>(), c->x_eslot.as<unsigned int>(),
                        c->x_ecnt.as<unsigned int>(), c->pair_key.as<unsigned long long>(),
                        c->pair_first.as<unsigned long long>(), c->pair_cnt.as<unsigned int>(), final_of_claim);
@@ -1364,14 +1332,14 @@ int bx_components_from_claims(amg_ctx* c) {
     cl.add(best2, (size_t)(2 * S + 2) * sizeof(unsigned int));
     cl.add(n_roots, sizeof(unsigned long long));
     AMGCHK(clear_many(c, cl));
-    hipLaunchKernelGGL(k_xc_init, dim3(blocks_for(S, 256)), dim3(256), 0, st, parent, S);
+    hipLaunchKernelGGL(k_xc_init, dim3(nblk(S, 256)), dim3(256), 0, st, parent, S);
     if (T > 1)
-      hipLaunchKernelGGL(k_xc_union, dim3(blocks_for(T, 256)), dim3(256), 0, st, c->tok_slot.as<int>(), T, parent);
-    hipLaunchKernelGGL(k_xc_flatten, dim3(blocks_for(S, 256)), dim3(256), 0, st, parent, S);
-    hipLaunchKernelGGL(k_xc_best, dim3(blocks_for(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
+      hipLaunchKernelGGL(k_xc_union, dim3(nblk(T, 256)), dim3(256), 0, st, c->tok_slot.as<int>(), T, parent);
+    hipLaunchKernelGGL(k_xc_flatten, dim3(nblk(S, 256)), dim3(256), 0, st, parent, S);
+    hipLaunchKernelGGL(k_xc_best, dim3(nblk(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
                        best2, n_roots);
     AMGCHK(x_rank_bitmap(c, best2, S, 1));  // non-roots keep {0, 0}: skipped like unclaimed ids
-    hipLaunchKernelGGL(k_xc_label, dim3(blocks_for(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
+    hipLaunchKernelGGL(k_xc_label, dim3(nblk(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
                        best2, c->s1.as<unsigned int>(), c->s5.as<long long>(), c->x_final.as<int>(),
                        c->node_comp.as<int>());
     FetchList l;

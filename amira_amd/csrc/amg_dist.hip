@@ -492,13 +492,11 @@ static int dest_counts(amg_ctx* c, long long n, long long n_real, int world, con
 static int nodes_local_x(amg_ctx* c, int k, int world, unsigned long long key_mask) {
   hipStream_t st = c->stream;
   for (int attempt = 0;; ++attempt) {
-    int which = 0;
+    Overflow which = OV_NONE;
     int r = bx_nodes_upsert(c, k, &which, true, false);  // (claims from the shard counters)
     if (r == AMG_OK) break;
-    if (r != AMG_E_OVERFLOW || which != 1 || attempt >= 8) return r;
-    ++c->retries;
-    if (c->node_slots >= (1ll << 30)) return amg_fail(AMG_E_OVERFLOW, "node table at maximum size");
-    c->node_slots = c->node_slots * 4 > (1ll << 30) ? (1ll << 30) : c->node_slots * 4;
+    if (r != AMG_E_OVERFLOW || which != OV_NODE_TABLE || attempt >= 8) return r;
+    AMGCHK(grow_after_overflow(c, which));
   }
   // claim ids in use lie below n (shard counters: with ids nobody took in between, first-seen 0)
   const long long n = c->x_nspace, T = c->n_tokens;
@@ -512,9 +510,10 @@ static int nodes_local_x(amg_ctx* c, int k, int world, unsigned long long key_ma
   AMGCHK(bucketing(c, n, &b));
   AMGCHK(c->dist_first.ensure((size_t)(n + 1) * sizeof(unsigned long long)));  // keys per claim
   if (n > 0)
+    // (x_two: dist_x implies !x_fp — bx_tuple_fits — so here and below it says "the TUPLE spills into the second word")
     hipLaunchKernelGGL(k_xd_node_keys, dim3(nblk(n, 256)), dim3(256), 0, st, c->node_tab.as<Slot16>(),
                        c->x_slot.as<unsigned int>(), c->x_first.as<unsigned int>(), n, k, c->x_bits,
-                       (long long)k * c->x_bits > 63 ? 1 : 0, c->seed, key_mask, (unsigned int)world,
+                       c->x_two ? 1 : 0, c->seed, key_mask, (unsigned int)world,
                        (world > 1 || n != c->n_local_nodes) ? 1 : 0, c->dist_first.as<unsigned long long>(), b.dest, b.idx);
   const int r = dest_counts(c, n, c->n_local_nodes, world, b);
   stage_end(c);
@@ -524,14 +523,13 @@ static int nodes_local_x(amg_ctx* c, int k, int world, unsigned long long key_ma
 static int edges_local_x(amg_ctx* c, int world) {
   hipStream_t st = c->stream;
   for (int attempt = 0;; ++attempt) {
-    int which = 0;
+    Overflow which = OV_NONE;
     int r = bx_edges_upsert(c, &which, false, true, false);
     if (r == AMG_OK) break;
-    if (r == AMG_E_OVERFLOW && which == 3)
+    if (r == AMG_E_OVERFLOW && which == OV_COLLISION)
       return amg_fail(AMG_E_COLLISION, "two gene-mers share a merge key: the merged build is repeated with the next seed");
-    if (r != AMG_E_OVERFLOW || which != 2 || attempt >= 8) return r;
-    ++c->retries;
-    c->edge_slots *= 4;
+    if (r != AMG_E_OVERFLOW || which != OV_EDGE_TABLE || attempt >= 8) return r;
+    AMGCHK(grow_after_overflow(c, which));
   }
   const long long n = c->x_espace, T = c->n_tokens;  // (claim ids in use lie below n: see nodes_local_x)
   stage_begin(c, "edge_count");
@@ -554,6 +552,7 @@ static int edges_local_x(amg_ctx* c, int world) {
 static int nodes_local(amg_ctx* c, DistState* d) {
   const int k = d->k, world = d->world;
   stages_reset(c);
+  c->sw = read_build_switches();  // (a merged build starts here)
   c->built = false;
   c->derive_ready = false;
   c->derived = false;
@@ -587,13 +586,11 @@ static int nodes_local(amg_ctx* c, DistState* d) {
   c->weak_fp_builds = weak ? 1 : 0;
   hipStream_t st = c->stream;
   for (int tries = 0;; ++tries) {
-    int which = 0;
+    Overflow which = OV_NONE;
     int r = bs_nodes_pass(c, k, &which);
     if (r == AMG_OK) break;
-    if (r != AMG_E_OVERFLOW || which != 1 || tries >= 8) return r;
-    ++c->retries;
-    if (c->node_slots >= (1ll << 30)) return amg_fail(AMG_E_OVERFLOW, "node table at maximum size");
-    c->node_slots = c->node_slots * 4 > (1ll << 30) ? (1ll << 30) : c->node_slots * 4;
+    if (r != AMG_E_OVERFLOW || which != OV_NODE_TABLE || tries >= 8) return r;
+    AMGCHK(grow_after_overflow(c, which));
   }
   // compaction list lives in s1 (first) / s3 (slot); destination order -> dist_a
   const long long n = c->n_local_nodes;
@@ -626,16 +623,15 @@ static int edges_local(amg_ctx* c, DistState* d) {
   hipStream_t st = c->stream;
   if (c->dist_x) return edges_local_x(c, world);
   for (int attempt = 0;; ++attempt) {
-    int which = 0;
+    Overflow which = OV_NONE;
     int r = bs_edges_pass(c, &which);
     if (r == AMG_OK) break;
-    if (r != AMG_E_OVERFLOW || which != 2 || attempt >= 8) {
-      if (which == 3)
+    if (r != AMG_E_OVERFLOW || which != OV_EDGE_TABLE || attempt >= 8) {
+      if (which == OV_COLLISION)
         return amg_fail(AMG_E_COLLISION, "fingerprint collision: the merged build is repeated with the next seed");
       return r;
     }
-    ++c->retries;
-    c->edge_slots *= 4;
+    AMGCHK(grow_after_overflow(c, which));
   }
   const long long n = c->n_local_pairs;
   {
@@ -910,7 +906,7 @@ static int hold_records(amg_ctx* c, DistState* d, int is_edge) {
     if (n > 0 && !is_edge)
       hipLaunchKernelGGL(k_xh_emit_nodes, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base,
                          c->s1.as<unsigned int>(), c->s5.as<long long>(), c->node_tab.as<Slot16>(),
-                         c->x_slot.as<unsigned int>(), c->k, c->x_bits, (long long)c->k * c->x_bits > 63 ? 1 : 0,
+                         c->x_slot.as<unsigned int>(), c->k, c->x_bits, c->x_two ? 1 : 0,
                          d->held.as<unsigned int>(), rb / 4, held_tok16(c->two_v) ? 1 : 0);
     else if (n > 0)
       hipLaunchKernelGGL(k_xh_emit_edges, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base,
@@ -1072,7 +1068,7 @@ static int nodes_global(amg_ctx* c, DistState* d) {
   if (nl > 0 && c->dist_x)
     hipLaunchKernelGGL(k_map_claims, dim3(nblk(nl, 256)), dim3(256), 0, st, rep, nl, send_order(c),
                        c->node_first.as<long long>(), n, c->node_tokens.as<int>(), c->node_tab.as<Slot16>(),
-                       c->x_slot.as<unsigned int>(), c->k, c->x_bits, (long long)c->k * c->x_bits > 63 ? 1 : 0,
+                       c->x_slot.as<unsigned int>(), c->k, c->x_bits, c->x_two ? 1 : 0,
                        c->x_final.as<int>(), status);
   else if (nl > 0)
     hipLaunchKernelGGL(k_map_slots, dim3(nblk(nl, 256)), dim3(256), 0, st, rep, nl, send_order(c),

@@ -124,6 +124,30 @@ struct StageTime {
 };
 
 static const uint64_t kAmgSeed0 = 0x9E3779B97F4A7C15ull;  // initial fingerprint seed (amg_build re-seeds on a collision)
+static const unsigned int kProbeLimit = 1024;             // slots a table pass looks at before it raises ST_OVERFLOW
+
+// The environment switches of a build (A/B and test switches), read ONCE where a build starts (build_impl, the merged
+// build's nodes_local) and consulted from ctx->sw by everything below.  Tests change them between builds of a process.
+struct BuildSwitches {
+  bool head_tiles_set = false;  // AMG_X_HEAD_TILES: tiles of a table pass's head launch (head_tiles) instead of
+  long long head_tiles = 0;     // head_tiles()'s rule
+  int claim_shards = -1;        // AMG_CLAIM_SHARDS: 0 / 1 claims from the shard counters never / always, -1 (unset) by size
+  bool tight_bits = false;      // AMG_X_TIGHT_BITS: as few bits per token as the vocabulary needs, not 16
+  bool key_fp = false;          // AMG_KEY_MODE=fp: the 32-byte fingerprint path of amg_build.hip
+  bool node_buckets = true;     // AMG_NODE_BUCKETS=0: hashed node slots only (k_nodes_v)
+  bool generic_k = false;       // AMG_X_GENERIC_K: the node kernel with k at run time for every k
+  bool rank_sort = false;       // AMG_X_RANK_SORT: radix sort instead of the bitmap ranking where both apply
+  int edge_lone = -1;           // AMG_EDGE_LONE: 0 never, 1 whenever the kernel allows it, -1 (unset) by the node count
+  bool edge_home = true;        // AMG_EDGE_HOME=0: no home slots in the edge table
+  bool no_derive = false;       // AMG_NO_DERIVE: never derive the rebuild from the graph at hand
+  int weak_fp = 0;              // AMG_TEST_WEAK_FP: attempts that use a 12-bit fingerprint
+  bool count_inline = false;    // AMG_COUNT_INLINE=1: one global atomic per window
+};
+BuildSwitches read_build_switches();  // amg_build.hip
+
+// why a table pass asks for the build to be repeated (AMG_E_OVERFLOW)
+enum Overflow { OV_NONE = 0, OV_NODE_TABLE = 1, OV_EDGE_TABLE = 2, OV_COLLISION = 3 };
+static inline int overflowed(Overflow* which, Overflow cause) { return *which = cause, AMG_E_OVERFLOW; }
 
 struct DistState;  // amg_dist.hip: communicator, buffers and progress of the ctx's merged builds
 struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until the caller has fetched it
@@ -226,6 +250,8 @@ struct amg_ctx {
   bool exact_keys = false;   // this build used the exact-key path
   int x_bits = 0;            // bits per token in the packed tuple
   bool x_fp = false;         // the tuple does not fit the slot: the key is its 94-bit fingerprint (amg_build_x.hip, x_fp94)
+  bool x_two = false;        // tuple or fingerprint spills into the slot's second word (set with x_bits / x_fp, as is:)
+  int x_kbits = 0;           // x_bits as the kernels take it: 0 for fingerprint keys
   int64_t x_nspace = 0, x_espace = 0;  // claim ids in use are below these (== n_nodes / n_pairs unless the
                                        // claims came from the shard counters: XShard in amg_x.h)
   int64_t x_max_claims = 0, x_max_eclaims = 0;  // capacity of the per-claim arrays (second half of x_first / x_efirst starts there)
@@ -287,6 +313,7 @@ struct amg_ctx {
   DevBuf cnt_list;     // k_count_ids: what the first sweep of a count found beyond its range, while that is little
   int cnt_sweeps[2] = {4, 4};  // sweeps the last node / edge-class count made use of (count_ids launches no more)
 
+  BuildSwitches sw;  // of the build in progress / the last one
   std::vector<StageTime> stages;
   bool timing = true;
 };
@@ -394,11 +421,12 @@ int derive_commit(amg_ctx* c, long long D2, long long P2);
 uint64_t pow2_at_least(uint64_t x);
 uint64_t slots_for(uint64_t n_keys);
 void bs_size_tables(amg_ctx* c);
+int grow_after_overflow(amg_ctx* c, Overflow cause);  // the next attempt's tables / seed; counts the retry
 int bs_read_stats(amg_ctx* c, int k, const ClearList* also = nullptr);
-int bs_nodes_pass(amg_ctx* c, int k, int* which);
+int bs_nodes_pass(amg_ctx* c, int k, Overflow* which);
 int bs_alloc_nodes(amg_ctx* c, long long D);
 int bs_nodes_rank_local(amg_ctx* c);
-int bs_edges_pass(amg_ctx* c, int* which);
+int bs_edges_pass(amg_ctx* c, Overflow* which);
 int bs_alloc_pairs(amg_ctx* c, long long P);
 int bs_pairs_from_local(amg_ctx* c);
 int bs_finish_from_pairs(amg_ctx* c);
@@ -407,13 +435,13 @@ int ensure_adjacency(amg_ctx* c);
 bool bx_applicable(const amg_ctx* c, int k);
 bool bx_fits(const amg_ctx* c, int k);
 bool bx_tuple_fits(const amg_ctx* c, int k);
-int bx_nodes(amg_ctx* c, int k, int* which);
-int bx_nodes_upsert(amg_ctx* c, int k, int* which, bool sharded = false, bool rank_follows = true);
+int bx_nodes(amg_ctx* c, int k, Overflow* which);
+int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded = false, bool rank_follows = true);
 int bx_nodes_rank(amg_ctx* c);
-int bx_edges(amg_ctx* c, int* which, unsigned int min_edge_cov = 0);
-int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, int* which);
+int bx_edges(amg_ctx* c, Overflow* which, unsigned int min_edge_cov = 0);
+int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, Overflow* which);
 int bx_flag_dead_reads(amg_ctx* c);
-int bx_edges_upsert(amg_ctx* c, int* which, bool lone = false, bool sharded = false, bool rank_follows = true);
+int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone = false, bool sharded = false, bool rank_follows = true);
 int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov = 0, bool nodes_counted = false);
 int bx_node_count(amg_ctx* c, bool tag);
 int count_ids(amg_ctx* c, int* ids, long long n, const Slot* gather_tab, long long n_ids,
