@@ -91,7 +91,7 @@ struct GapArgs {
   int* cand;               // candidate scratch, [grid threads * cand_stride]
   unsigned int cand_stride;
   unsigned char* final_cls;
-  unsigned char* need_slow;  // per gapped read: 1 = the wave-per-read fast kernel gave up
+  unsigned char* need_slow;  // per gapped read: non-zero = the wave-per-read fast kernel gave up (a GS_* code: why)
   // path memo (k_gap_queries / k_gap_dfs): the same (start node, direction, end node) question is asked by every read
   // that lost the same stretch of the genome — about nine times each at 3 000x depth — and answered once
   const int* gq;             // per gapped read GF_MAXGAP query slots in run order; [0] < 0: no memo for this read
@@ -109,6 +109,26 @@ struct GapArgs {
 #define LEAN_CHUNK 32  // gapped reads per workgroup when k_corr_gapped_fast works through k_corr_gapped_lean's left-overs
 #define CLS_READS 64   // reads per wave of k_corr_classify
 #define PACK_READS 64  // reads per wave of k_corr_pack
+// why a read was handed down a tier: what need_slow[gi] (wave-per-read kernel -> k_corr_gapped) and the lean kernel's
+// flag (k_corr_gapped_lean -> k_corr_gapped_fast) hold.  The consumers test for non-zero; the route report
+// (AMG_CORR_ROUTES, amg_correct_routes.hip) tallies the codes.
+enum {
+  GS_NOT_TRIED = 1,   // the pre-fill 0x01010101 of AMG_NO_FAST_GAPPED: the wave-per-read kernel did not run
+  GS_WINDOWS = 2,     // more than GF_MAXW windows
+  GS_RUNS = 3,        // more than GF_MAXGAP None runs
+  GS_MEMO_UNFIT = 4,  // a memo answer that did not fit (its pool, or GF_POOL ints inside k_gap_dfs)
+  GS_RECORDS = 5,     // the read's path records exceed GF_POOL ints
+  GS_COMBOS = 6,      // more than GF_MAXCOMBO candidates
+  GS_CAND = 7,        // a candidate longer than GF_CAND nodes
+  GS_CODES = 8
+};
+enum {
+  GL_NO_SLOTS = 1,  // no memo slots for the read (more than 64 windows or GF_MAXGAP runs)
+  GL_ANSWERS = 2,   // a question without exactly one answer (none, several, or one that did not fit)
+  GL_LONG = 3,      // a single answer longer than GM_INLINE ints
+  GL_OTHER = 4,     // a path of one node (or a run without a slot)
+  GL_CODES = 5
+};
 
 // ---- position carry-over (amg_correct_nw.hip)
 // what k_corr_nw_fast takes: N corrected genes against M original ones (k_nw_sizes decides with the same rule)
@@ -167,6 +187,9 @@ struct CorrSwitches {
   int fast_nw;              // AMG_NO_FAST_NW: every carry-over through the general kernel
   int nw_shortcuts;         // AMG_NW_NO_SHORTCUT: k_corr_nw_fast fills a matrix for every read
   const char* node_bound;   // AMG_TEST_NODE_BOUND=<n>: test hook, a node bound that does not hold (nullptr: unset)
+  bool routes;              // AMG_CORR_ROUTES=1: test hook, tally which read took which route (amg_correct_routes)
+  const char* gap_pool;     // AMG_TEST_GAP_POOL=<n>: test hook, ints of k_corr_gapped's path pool at the first attempt
+  const char* memo_spill;   // AMG_TEST_MEMO_SPILL=<n>: test hook, ints of the memo pool behind the inline stretches
 };
 
 // The scratch plan: every array of a call that is carved out of a shared buffer, under the name the steps use.
@@ -203,6 +226,9 @@ struct CorrCounts {
   bool carry = false;  // positions are carried over: there are gapped reads and gene positions
   long long out_reads = 0, out_tokens = 0, big_total = 0, pos_total = 0;  // shape
   unsigned long long n_general = 0;
+  long long n_queries = 0;   // gapped: questions of the path memo (0 without memo)
+  int pool_retries = 0;      // gapped: attempts of k_corr_gapped beyond the first
+  bool lean_ran = false, fast_ran = false, memo = false;
 };
 
 // the position pools of the CURRENT reads (the only fields the gather kernels of amg_corrected.hip read); again
@@ -220,10 +246,17 @@ static void fill_pos_args(amg_ctx* c, CorrArgs& a) {
 // k_corr_classify alone (it lives in amg_correct_gapped.hip, see there; its step is amg_correct.hip's)
 void corr_classify_launch(amg_ctx* c, const CorrArgs& a);
 // stage correct_gapped: a has tmp_tok; writes the staged genes, new_len and final_cls of the gapped reads
-int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n);
+int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, CorrCounts& n);
 // inside the shape step: sizes of the carry-over's scratch and products, their totals appended to `shape`
 int corr_nw_sizes(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, long long n_gapped,
                   FetchList& shape);
 // stage correct_positions: room for what this call produces (may MOVE the pools: fill_pos_args again), then the kernels
 int corr_grow_pos_pools(amg_ctx* c, const CorrCounts& n);
 int corr_positions(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n);
+
+// ---- route report (amg_correct_routes.hip), only with CorrSwitches::routes: small tally kernels behind the steps
+int routes_begin(amg_ctx* c);
+// at the end of corr_gapped, while need_slow (a borrowed output buffer) and the lean kernel's flags still hold
+int routes_gapped(amg_ctx* c, const CorrScratch& S, const CorrCounts& n, const unsigned char* need_slow, const int* gq);
+int routes_nw(amg_ctx* c, const CorrScratch& S, const CorrCounts& n);  // from the NwRec records, sizes and final_cls
+int routes_end(amg_ctx* c, const CorrCounts& n);                       // the call's one extra read-back

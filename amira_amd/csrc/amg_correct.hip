@@ -117,17 +117,20 @@ __global__ __launch_bounds__(256) void k_corr_pack(PackArgs A) {
 
 // ------------------------------------------------------------------ the host's view of one call
 static CorrSwitches read_switches() {
-  auto off = [](const char* name) {
+  auto is_one = [](const char* name) {
     const char* v = getenv(name);
     return v && v[0] == '1';
   };
   CorrSwitches sw;
-  sw.gap_memo = !off("AMG_NO_GAP_MEMO");
-  sw.fast_gapped = !off("AMG_NO_FAST_GAPPED");
-  sw.lean_gapped = !off("AMG_NO_LEAN_GAPPED");
-  sw.fast_nw = !off("AMG_NO_FAST_NW");
-  sw.nw_shortcuts = !off("AMG_NW_NO_SHORTCUT");
+  sw.gap_memo = !is_one("AMG_NO_GAP_MEMO");
+  sw.fast_gapped = !is_one("AMG_NO_FAST_GAPPED");
+  sw.lean_gapped = !is_one("AMG_NO_LEAN_GAPPED");
+  sw.fast_nw = !is_one("AMG_NO_FAST_NW");
+  sw.nw_shortcuts = !is_one("AMG_NW_NO_SHORTCUT");
   sw.node_bound = getenv("AMG_TEST_NODE_BOUND");
+  sw.routes = is_one("AMG_CORR_ROUTES");  // (the one switch that turns something ON)
+  sw.gap_pool = getenv("AMG_TEST_GAP_POOL");
+  sw.memo_spill = getenv("AMG_TEST_MEMO_SPILL");
   return sw;
 }
 
@@ -336,6 +339,8 @@ extern "C" int amg_correct_reads(amg_ctx* c, int64_t* n_out_reads, int64_t* n_ou
   CorrArgs a;
   AMGCHK(plan_per_read(c, S));
   corr_args(c, S, a);  // (no tmp_tok yet)
+  c->have_routes = false;
+  if (sw.routes) AMGCHK(routes_begin(c));
 
   stage_begin(c, "correct_classify");
   AMGCHK(corr_classify(c, S, a, n));
@@ -362,6 +367,7 @@ extern "C" int amg_correct_reads(amg_ctx* c, int64_t* n_out_reads, int64_t* n_ou
     AMGCHK(corr_grow_pos_pools(c, n));
     corr_args(c, S, a);  // the pools of produced positions where they are now
     AMGCHK(corr_positions(c, sw, S, a, n));
+    if (sw.routes) AMGCHK(routes_nw(c, S, n));
     stage_end(c);
   }
 
@@ -369,6 +375,7 @@ extern "C" int amg_correct_reads(amg_ctx* c, int64_t* n_out_reads, int64_t* n_ou
   AMGCHK(corr_pack(c, S, a, n));
   AMGCHK(corr_node_bound(c, sw, S, n));
   stage_end(c);
+  if (sw.routes) AMGCHK(routes_end(c, n));
   c->c_reads = n.out_reads;
   c->c_tokens = n.out_tokens;
   c->c_pos1_used = c->pos1_used + (n.carry ? n.pos_total : 0);  // becomes current with amg_adopt_corrected

@@ -677,6 +677,12 @@ __global__ __launch_bounds__(GL_THREADS) void k_corr_gapped_lean(GapArgs A, cons
   const bool good = !mine || (slot >= 0 && res.z == 1 && res.y >= 6 && res.y <= GM_INLINE && len >= 2);
   // every run of the read has to qualify: the group's 16 bits of the wave's ballot
   const unsigned int bad16 = (unsigned int)((__ballot(!good) >> sh) & 0xffffull);
+  // why the read is left (GL_*): the weightiest reason among its runs
+  const bool multi = !good && slot >= 0 && res.z != 1;
+  const bool toolong = !good && slot >= 0 && res.z == 1 && res.y > GM_INLINE;
+  const unsigned int multi16 = (unsigned int)((__ballot(multi) >> sh) & 0xffffull);
+  const unsigned int long16 = (unsigned int)((__ballot(toolong) >> sh) & 0xffffull);
+  const int why = !ok ? GL_NO_SLOTS : multi16 ? GL_ANSWERS : long16 ? GL_LONG : GL_OTHER;  // (looked at when bad16 != 0)
   ok = ok && bad16 == 0u;
   // does the next run start where this one ends?  (its ps from the neighbouring lane: row_shl:1)
   const int ps_next = __builtin_amdgcn_update_dpp(-1, ps, 0x101, 0xf, 0xf, false);
@@ -706,7 +712,7 @@ __global__ __launch_bounds__(GL_THREADS) void k_corr_gapped_lean(GapArgs A, cons
   }
   // the reads left to the wave-per-read kernel: a flag per read (a list would need a counter, and one counter word
   // takes ~100 returning atomics per microsecond: 30 k waves with a read to hand over were 0.3 ms of this kernel)
-  if (have && l16 == 0) left[gi] = ok ? 0 : 1;
+  if (have && l16 == 0) left[gi] = (unsigned char)(ok ? 0 : why);
 }
 
 // GF_WPB reads (waves) per workgroup.  The LDS of a workgroup is held until its LAST wave is done
@@ -746,7 +752,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
   const int nwin = L0 - g.k + 1;
   const int start = rec.start, end = rec.end;
   if (nwin > GF_MAXW) {
-    if (lane == 0) A.need_slow[gi] = 1;
+    if (lane == 0) A.need_slow[gi] = GS_WINDOWS;
     return;
   }
   int* W = s_node[wv];
@@ -782,7 +788,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
     n_gaps += __popcll(m);
   }
   if (n_gaps > GF_MAXGAP) {
-    if (lane == 0) A.need_slow[gi] = 1;
+    if (lane == 0) A.need_slow[gi] = GS_RUNS;
     return;
   }
   wave_sync();
@@ -791,6 +797,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
   // wave-cooperative DFS per run
   const bool memo = __builtin_amdgcn_readfirstlane(myslot) >= 0;
   bool bad = false;
+  int why = GS_RECORDS;
   if (memo) {
     int4 res = make_int4(0, 0, 0, 0);
     if (lane < n_gaps) res = A.qres[myslot];
@@ -804,6 +811,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
     const int total = __shfl(at, n_gaps - 1, 64);
     at -= len;
     bad = __any(res.y < 0) || total > GF_POOL;
+    if (__any(res.y < 0)) why = GS_MEMO_UNFIT;
     if (!bad) {
       for (int q = 0; q < n_gaps; ++q) {
         const int src = __shfl(res.x, q, 64), ln = __shfl(len, q, 64), dst0 = __shfl(at, q, 64);
@@ -826,7 +834,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
     }
   }
   if (bad) {
-    if (lane == 0) A.need_slow[gi] = 1;
+    if (lane == 0) A.need_slow[gi] = (unsigned char)why;
     return;
   }
   wave_sync();
@@ -848,7 +856,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
     return;
   }
   if (n_combo > GF_MAXCOMBO) {
-    if (lane == 0) A.need_slow[gi] = 1;
+    if (lane == 0) A.need_slow[gi] = GS_COMBOS;
     return;
   }
   int* CN = s_cnode[wv];
@@ -917,7 +925,7 @@ __device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi,
     }
     wave_sync();
     if (n < 0) {
-      if (lane == 0) A.need_slow[gi] = 1;
+      if (lane == 0) A.need_slow[gi] = GS_CAND;
       return;
     }
     const int ng = n + g.k - 1;
@@ -1009,7 +1017,7 @@ __global__ void k_scatter_gapped(const unsigned int* __restrict__ flag, const lo
 // ------------------------------------------------------------------ stage correct_gapped
 // Path memo: every distinct (start, direction, end) question of the None runs is answered once.  Returns in *gq the
 // per-read question slots, nullptr when there is no memo (switched off, no runs, or offsets beyond an int).
-static int gap_memo(amg_ctx* c, const CorrArgs& a, const CorrCounts& n, const int** gq) {
+static int gap_memo(amg_ctx* c, const CorrSwitches& sw, const CorrArgs& a, CorrCounts& n, const int** gq) {
   hipStream_t st = c->stream;
   const long long n_gapped = n.n_gapped, total_runs = n.total_runs;
   *gq = nullptr;
@@ -1039,7 +1047,11 @@ static int gap_memo(amg_ctx* c, const CorrArgs& a, const CorrCounts& n, const in
   if (v[1]) return amg_fail(AMG_E_HIP, "correct_reads: path memo table full");
   const long long n_queries = (long long)v[0];
   // answers average ~20 ints; one that does not find room sends its reads to the general kernel
-  const unsigned long long qcap = (unsigned long long)n_queries * (GM_INLINE + 32ull) + 4096ull;
+  unsigned long long qcap = (unsigned long long)n_queries * (GM_INLINE + 32ull) + 4096ull;
+  if (sw.memo_spill) {  // test hook: less room behind the inline stretches (never more)
+    const unsigned long long lo = (unsigned long long)n_queries * GM_INLINE + strtoull(sw.memo_spill, nullptr, 10);
+    qcap = lo < qcap ? lo : qcap;
+  }
   if (qcap > 0x7fffffffull) return AMG_OK;  // (pool offsets are ints)
   AMGCHK(c->gm_pool.ensure((size_t)qcap * sizeof(int)));
   AMGCHK(c->gm_gene.ensure((size_t)qcap * sizeof(int)));
@@ -1048,6 +1060,7 @@ static int gap_memo(amg_ctx* c, const CorrArgs& a, const CorrCounts& n, const in
                        n_queries, c->gm_tab.as<unsigned long long>(), c->gm_ctr.as<unsigned long long>() + 1, qcap,
                        c->gm_pool.as<int>(), c->gm_res.as<int4>(), c->gm_gene.as<int>());
   *gq = c->gm_q.as<int>();
+  n.n_queries = n_queries;
   return AMG_OK;
 }
 
@@ -1055,7 +1068,7 @@ static int gap_memo(amg_ctx* c, const CorrArgs& a, const CorrCounts& n, const in
 // answer and flags the others in gm_fail; k_corr_gapped_fast (a wave per read, LDS staging) does those — or, without
 // memo or lean kernel, every read — and flags in need_slow what exceeds its capacities; k_corr_gapped (a thread per
 // read, global pool and candidate scratch) does the flagged rest and is the one that may ask for a larger pool.
-int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n) {
+int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, CorrCounts& n) {
   hipStream_t st = c->stream;
   const long long R = c->n_reads, n_gapped = n.n_gapped;
   AMGCHK(S.glist->ensure((size_t)(n_gapped + 1) * sizeof(int)));
@@ -1063,12 +1076,16 @@ int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const 
   hipLaunchKernelGGL(k_scatter_gapped, dim3(nblk(R, 256)), dim3(256), 0, st, S.flag, S.new_idx, R,
                      S.glist->as<int>(), a.read_off, S.r_start, S.r_end, S.tmp_off, a.lmask, c->gap_rec.as<GapRec>());
   const int* gq = nullptr;
-  if (n.total_runs > 0 && sw.gap_memo) AMGCHK(gap_memo(c, a, n, &gq));
+  if (n.total_runs > 0 && sw.gap_memo) AMGCHK(gap_memo(c, sw, a, n, &gq));
   const unsigned int threads_total = 64u * 2048u;
   unsigned int cand_stride = (unsigned int)(2 * n.max_bound + (n.max_bound + 3) / 4 + c->k + 16);
   AMGCHK(S.cand->ensure((size_t)threads_total * cand_stride * sizeof(int)));
   // the general kernel only sees what the fast kernel hands over: start small, grow on demand
   unsigned long long pool_cap = 1ull << 22;
+  if (sw.gap_pool) {  // test hook: a first pool that the reads of a small input overflow (never a larger one)
+    const unsigned long long lo = strtoull(sw.gap_pool, nullptr, 10);
+    pool_cap = lo < pool_cap ? lo : pool_cap;
+  }
   AMGCHK(S.need_slow->ensure((size_t)n_gapped + 64));
   unsigned char* need_slow = S.need_slow->as<unsigned char>();
   for (int attempt = 0;; ++attempt) {
@@ -1097,7 +1114,8 @@ int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const 
       gcl.add(need_slow, ((size_t)n_gapped + 4) & ~(size_t)3, sw.fast_gapped ? 0u : 0x01010101u);  // (the buffer has 64 spare bytes)
       AMGCHK(clear_many(c, gcl));
       if (sw.fast_gapped && gq && sw.lean_gapped) {
-        // (no count of the flagged reads comes back to the host)
+        // (no count of the flagged reads comes back to the host; AMG_CORR_ROUTES tallies them for tests)
+        n.lean_ran = true;
         AMGCHK(c->gm_fail.ensure((size_t)n_gapped + 64));
         hipLaunchKernelGGL(k_corr_gapped_lean, dim3(nblk(n_gapped, GL_THREADS / GL_GROUP)), dim3(GL_THREADS), 0, st, G,
                            c->gm_gene.as<int>(), c->gm_fail.as<unsigned char>());
@@ -1118,6 +1136,8 @@ int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const 
     if (!hs[ST_OVERFLOW]) break;
     if (attempt >= 8) return amg_fail(AMG_E_OVERFLOW, "correct_reads: path pool overflow");
     pool_cap = hs[ST_COMPACT_A] * 2 + (1ull << 20);
+    n.pool_retries = attempt + 1;
   }
+  if (sw.routes) AMGCHK(routes_gapped(c, S, n, need_slow, gq));  // (need_slow is a borrowed output buffer: now)
   return AMG_OK;
 }

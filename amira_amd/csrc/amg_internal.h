@@ -304,9 +304,13 @@ struct amg_ctx {
   DevBuf gm_q;         // int32 [gapped reads x GF_MAXGAP] question slot per None run
   DevBuf gm_pool;      // int32 path records
   DevBuf gm_gene;      // int32 per pool entry of a one-answer question: last gene of the path node (k_corr_gapped_lean)
-  DevBuf gm_fail;      // uint8 [gapped reads] 1: the sixteen-lanes-per-read kernel left the read to the wave-per-read one
+  DevBuf gm_fail;      // uint8 [gapped reads] non-zero: the sixteen-lanes-per-read kernel left the read to the wave-per-read one (a GL_* code: why)
   DevBuf gm_ctr;       // uint64[4]         {questions listed, pool ints used}
   DevBuf nw_rec;       // per gapped read: the record k_corr_nw_fast starts from
+  // route report of the last amg_correct_reads call made with AMG_CORR_ROUTES=1 (amg_correct_routes.hip; tests)
+  DevBuf routes_dev;   // uint64[AMG_ROUTE_WORDS] tallies on the device during such a call
+  bool have_routes = false;
+  int64_t routes[AMG_ROUTE_WORDS] = {0};
   DevBuf bnd_bits;     // uint32[(n_tokens >> 5) + pad]: bit t set when a read ends at token t
   DevBuf cnt_state;    // counting sweeps: per-sweep left-over counts and done flags + the hints
   bool cnt_hint_reset = false;

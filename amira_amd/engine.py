@@ -239,6 +239,17 @@ class Engine:
         check(_ffi.lib.amg_correct_reads(self._h, C.byref(nr), C.byref(nt)))
         return nr.value, nt.value
 
+    ROUTES = ("gapped", "by_lean", "by_fast", "by_general", "on_not_tried", "on_windows", "on_runs", "on_memo_unfit",
+              "on_records", "on_combos", "on_cand", "lean_no_slots", "lean_answers", "lean_long", "lean_other",
+              "no_memo_slots", "memo_questions", "memo_spilled", "memo_unfit", "pool_retries", "keep_orig",
+              "nw_fast", "nw_lds", "nw_global")
+
+    def correct_routes(self):
+        """tallies of the last correct_reads() made with AMG_CORR_ROUTES=1 (include/amg.h, AMG_ROUTE_*): a test hook"""
+        out = np.zeros(len(self.ROUTES), np.int64)
+        check(_ffi.lib.amg_correct_routes(self._h, _ffi.ptr(out), len(out)))
+        return dict(zip(self.ROUTES, out.tolist()))
+
     def corrected(self, n_reads, n_tokens, with_positions, buf=None, pos32=False):
         """the corrected set on the host.  pos32: the positions as int32 arrays (gathered on the device, half the bytes
         over PCIe) when every one of them fits — int64 otherwise, as without the flag"""

@@ -447,6 +447,41 @@ int amg_set_timing(amg_ctx* ctx, int on);
  *    cov (uint32), sdir, tdir (int8), alive (uint8) over 2n edges each. */
 int amg_scan_probe(amg_ctx* ctx, int kind, const void* in, int64_t n, int64_t* out, void* aux);
 
+/* ---- tests: which read took which route through the last amg_correct_reads call ----------------------
+ * With AMG_CORR_ROUTES=1 in the environment of an amg_correct_reads call, small tally kernels run behind its steps
+ * (without it the call launches and reads back what it always did).  amg_correct_routes copies the tallies of the
+ * last such call: out[i] for i < min(cap, AMG_ROUTE_WORDS), indexed as below; returns AMG_E_STATE when the last
+ * call ran without the switch.  "handed on" = left by the wave-per-read kernel to the general one, by reason;
+ * "lean left" = left by the sixteen-lanes-per-read kernel to the wave-per-read one, by reason. */
+enum {
+  AMG_ROUTE_GAPPED = 0,        /* reads with None runs (re-threaded) */
+  AMG_ROUTE_BY_LEAN = 1,       /* finished by k_corr_gapped_lean */
+  AMG_ROUTE_BY_FAST = 2,       /* finished by k_corr_gapped_fast */
+  AMG_ROUTE_BY_GENERAL = 3,    /* finished by k_corr_gapped */
+  AMG_ROUTE_ON_NOT_TRIED = 4,  /* handed on: the wave-per-read kernel did not run */
+  AMG_ROUTE_ON_WINDOWS = 5,    /* handed on: more windows than the kernel stages */
+  AMG_ROUTE_ON_RUNS = 6,       /* handed on: more None runs */
+  AMG_ROUTE_ON_MEMO_UNFIT = 7, /* handed on: a memo answer that did not fit */
+  AMG_ROUTE_ON_RECORDS = 8,    /* handed on: path records beyond the staging */
+  AMG_ROUTE_ON_COMBOS = 9,     /* handed on: too many candidates */
+  AMG_ROUTE_ON_CAND = 10,      /* handed on: a candidate too long */
+  AMG_ROUTE_LEAN_NO_SLOTS = 11, /* lean left: the read has no memo slots */
+  AMG_ROUTE_LEAN_ANSWERS = 12,  /* lean left: a question without exactly one answer */
+  AMG_ROUTE_LEAN_LONG = 13,     /* lean left: a single answer beyond the inline stretch */
+  AMG_ROUTE_LEAN_OTHER = 14,    /* lean left: a path of one node */
+  AMG_ROUTE_NO_MEMO_SLOTS = 15, /* gapped reads that searched for themselves (no memo, or none for them) */
+  AMG_ROUTE_MEMO_QUESTIONS = 16,
+  AMG_ROUTE_MEMO_SPILLED = 17,  /* answers kept behind the inline stretches */
+  AMG_ROUTE_MEMO_UNFIT = 18,    /* answers that did not fit */
+  AMG_ROUTE_POOL_RETRIES = 19,  /* repeats of the general kernel with a larger path pool */
+  AMG_ROUTE_KEEP_ORIG = 20,     /* reads kept with their original genes (a run without a path) */
+  AMG_ROUTE_NW_FAST = 21,       /* positions carried over by k_corr_nw_fast */
+  AMG_ROUTE_NW_LDS = 22,        /* by k_corr_nw with its matrix in LDS */
+  AMG_ROUTE_NW_GLOBAL = 23,     /* by k_corr_nw with global scratch */
+  AMG_ROUTE_WORDS = 24
+};
+int amg_correct_routes(amg_ctx* ctx, int64_t* out, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

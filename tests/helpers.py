@@ -170,3 +170,25 @@ def live_arrays(obj, with_adj=True):
         out["adj_off"] = np.concatenate([[0], np.cumsum(row_cnt[rows])])
         out["adj"] = emap[adj[keep]]
     return out
+
+
+def flat_positions(read_ids, reads, pos):
+    gs = np.fromiter((p[0] for r in read_ids for p in pos[r]), dtype=np.int64)
+    ge = np.fromiter((p[1] for r in read_ids for p in pos[r]), dtype=np.int64)
+    assert len(gs) == sum(len(reads[r]) for r in read_ids)
+    return gs, ge
+
+
+def check_corrected(eng, vocab, read_ids, want_genes, want_pos):
+    n_reads, n_tokens = eng.correct_reads()
+    out = eng.corrected(n_reads, n_tokens, want_pos is not None)
+    got_ids = [read_ids[i] for i in out["orig_read"]]
+    assert got_ids == list(want_genes.keys())
+    offs = out["read_offsets"]
+    for i, rid in enumerate(got_ids):
+        a, b = int(offs[i]), int(offs[i + 1])
+        assert vocab.decode(out["tokens"][a:b]) == list(want_genes[rid]), rid
+        if want_pos is not None:
+            got = list(zip(out["gene_start"][a:b].tolist(), out["gene_end"][a:b].tolist()))
+            assert got == [tuple(p) for p in want_pos[rid]], rid
+    return got_ids, out

@@ -31,6 +31,16 @@ def test_binding_covers_the_header():
     assert sorted(_ffi.SYMBOLS) == declared_symbols()
 
 
+def test_route_names_follow_the_header():
+    """Engine.ROUTES labels the words of amg_correct_routes in the order of the AMG_ROUTE_* enum of include/amg.h"""
+    from amira_amd import Engine
+    text = open(os.path.join(ROOT, "include", "amg.h")).read()
+    enum = re.findall(r"\bAMG_ROUTE_([A-Z_]+)\s*=\s*(\d+)", text)
+    assert enum[-1][0] == "WORDS" and [int(v) for _, v in enum] == list(range(len(enum)))
+    assert int(enum[-1][1]) == len(Engine.ROUTES)
+    assert tuple(n.lower() for n, _ in enum[:-1]) == Engine.ROUTES
+
+
 def test_no_cpu_fallback():
     """Without a HIP device the product must raise, not compute on the host."""
     import torch

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import procedures as P
-from helpers import compare_engine_to_oracle, oracle_arrays
+from helpers import check_corrected, compare_engine_to_oracle, flat_positions, oracle_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -16,28 +16,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def flat_positions(read_ids, reads, pos):
-    gs = np.fromiter((p[0] for r in read_ids for p in pos[r]), dtype=np.int64)
-    ge = np.fromiter((p[1] for r in read_ids for p in pos[r]), dtype=np.int64)
-    assert len(gs) == sum(len(reads[r]) for r in read_ids)
-    return gs, ge
-
-
-def check_corrected(eng, vocab, read_ids, want_genes, want_pos):
-    n_reads, n_tokens = eng.correct_reads()
-    out = eng.corrected(n_reads, n_tokens, want_pos is not None)
-    got_ids = [read_ids[i] for i in out["orig_read"]]
-    assert got_ids == list(want_genes.keys())
-    offs = out["read_offsets"]
-    for i, rid in enumerate(got_ids):
-        a, b = int(offs[i]), int(offs[i + 1])
-        assert vocab.decode(out["tokens"][a:b]) == list(want_genes[rid]), rid
-        if want_pos is not None:
-            got = list(zip(out["gene_start"][a:b].tolist(), out["gene_end"][a:b].tolist()))
-            assert got == [tuple(p) for p in want_pos[rid]], rid
-    return got_ids, out
 
 
 DERIVED = []   # per run_sweep: was the third graph made from the second one's live part (amg_derive.hip)?
@@ -226,18 +204,24 @@ def test_borrowed_device_inputs(eng):
     assert np.array_equal(cov_a, cov_b)
 
 
-def _tandem_reads(seed, n_reads, L, err):
+TANDEM_ARRAYS = ((12, "t0", 9), (33, "t1", 6), (50, "t2", 12))
+
+
+def _tandem_reads(seed, n_reads, L, err, glen=60, arrays=TANDEM_ARRAYS, lengths=None):
     """reads over a genome with tandem gene arrays: corrected and original gene lists of such
     reads are near-periodic, so shifted alignments tie with the diagonal one (the position
-    carry-over may then not take its equal-length shortcut)"""
+    carry-over may then not take its equal-length shortcut).  glen genes before the arrays go in; with `lengths` read
+    r has lengths[r % len(lengths)] genes instead of L"""
     from amira_amd import synth
     rng = np.random.default_rng(seed)
-    genome = [(1 if rng.random() < 0.5 else -1, f"g{i}") for i in range(60)]
-    for at, name, n in ((12, "t0", 9), (33, "t1", 6), (50, "t2", 12)):
+    genome = [(1 if rng.random() < 0.5 else -1, f"g{i}") for i in range(glen)]
+    for at, name, n in arrays:
         genome[at:at] = [(1, name)] * n
     names = sorted({g for _, g in genome})
     reads = {}
     for r in range(n_reads):
+        if lengths is not None:
+            L = int(lengths[r % len(lengths)])
         s0 = int(rng.integers(0, len(genome) - L + 1))
         seq = list(genome[s0:s0 + L])
         if rng.random() < 0.5:

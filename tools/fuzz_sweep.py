@@ -60,9 +60,33 @@ def run(budget, seed, max_cases=None):
     rng = np.random.default_rng(seed)
     eng = Engine(0)
     t_end = time.time() + budget
+    # what the corrections covered: every second case runs with the route report (AMG_CORR_ROUTES=1) and its tallies
+    # are added up (no assertion on them); the cases between go through the plain call, as shipped
+    routes, env_before, plain_correct = {}, os.environ.get("AMG_CORR_ROUTES"), eng.correct_reads
+
+    def correct_and_tally():
+        out = plain_correct()
+        if os.environ.get("AMG_CORR_ROUTES") == "1":
+            for name, v in eng.correct_routes().items():
+                routes[name] = routes.get(name, 0) + v
+        return out
+    eng.correct_reads = correct_and_tally
+    try:
+        return _run(eng, rng, t_end, max_cases, seed, routes)
+    finally:
+        del eng.correct_reads
+        if env_before is None:
+            os.environ.pop("AMG_CORR_ROUTES", None)
+        else:
+            os.environ["AMG_CORR_ROUTES"] = env_before
+        eng.close()
+
+
+def _run(eng, rng, t_end, max_cases, seed, routes):
     n_ok = n_pal = n_fail = 0
     while time.time() < t_end and (max_cases is None or n_ok + n_pal + n_fail < max_cases):
         reads, k, info = make_case(rng)
+        os.environ["AMG_CORR_ROUTES"] = "1" if (n_ok + n_pal + n_fail) % 2 == 0 else "0"
         pos = synth.positions_for(reads)
         fq = P.FakeFastq(synth.fake_fastq_lengths(reads))
         try:
@@ -112,7 +136,8 @@ def run(budget, seed, max_cases=None):
         if n_fail >= 5:
             break
     print(f"fuzz: {n_ok} sweeps equal to the oracle, {n_pal} palindrome assertions on both sides, {n_fail} failures (seed {seed})")
-    eng.close()
+    if routes:
+        print("fuzz routes (every second case):", " ".join(f"{name}={v}" for name, v in routes.items() if v))
     return n_ok, n_pal, n_fail
 
 
