@@ -149,7 +149,7 @@ BuildSwitches read_build_switches();  // amg_build.hip
 enum Overflow { OV_NONE = 0, OV_NODE_TABLE = 1, OV_EDGE_TABLE = 2, OV_COLLISION = 3 };
 static inline int overflowed(Overflow* which, Overflow cause) { return *which = cause, AMG_E_OVERFLOW; }
 
-struct DistState;  // amg_dist.hip: communicator, buffers and progress of the ctx's merged builds
+struct DistState;  // amg_dist.h: communicator, buffers and progress of the ctx's merged builds
 struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until the caller has fetched it
 
 struct amg_ctx {
@@ -268,12 +268,9 @@ struct amg_ctx {
   DevBuf x_first_all;        // uint32[claims] filtered build: ~first_seen of EVERY claim (k_x_drop_claims zeroes x_first)
   bool comp_from_claims = false;  // filtered build: component ids come from the claims (bx_components_from_claims)
 
-  // ---- multi-GPU merge (amg_dist.hip)
+  // ---- multi-GPU merge (amg_dist.hip): what the builds and the correction read; the merge's own state is *dist
   int world = 1;
   uint32_t dist_min_node = 1, dist_min_edge = 1;  // fused filter of the next merged build
-  int64_t dist_nspace = 0;   // ids the current bucketing ran over (local records + claim ids nobody took)
-  bool dist_sorted = false;  // the local records leave in sorted order (send_order)
-  DevBuf dist_a, dist_cnt, dist_first, dist_slot, dist_gtab, dist_lcnt;
   DistState* dist = nullptr;
   BubbleState* bub = nullptr;  // amg_bubbles.hip
 
