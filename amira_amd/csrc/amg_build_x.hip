@@ -1,7 +1,7 @@
 // amg_build_x.hip — the single-GPU build in 16-byte slots with claim ids: EXACT tuple keys, or verified 94-bit
 // fingerprints of the tuple in the same slots.
 //
-// Same result as the 32-byte fingerprint path of amg_build.hip (GeneMerGraph.__init__, reference construct_graph.py:31-102),
+// Same result as the 32-byte fingerprint path of amg_build_fp.hip (GeneMerGraph.__init__, reference construct_graph.py:31-102),
 // different bookkeeping.  The canonical k-tuple itself is the key whenever it fits 94 bits (k * ceil(log2(2V)) <= 94:
 // k = 3 for any vocabulary, k = 5 up to 2^18 genes); a longer tuple is keyed by its 94-bit fingerprint and every window
 // is verified against its key's first occurrence (next section).  The 32-byte path is still taken for 2^29 tokens and
@@ -1077,7 +1077,7 @@ int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, Overflow* which) 
   const long long n = c->x_nspace, T = c->n_tokens;
   stage_begin(c, "node_count");  // per claim, straight from the per-window claims (construct_node.py:33-36)
   AMGCHK(c->x_ecnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, c->tok_slot.as<int>(), T, nullptr, n, c->x_ecnt.as<unsigned int>(), 4));
+  AMGCHK(count_ids(c, CountNodes, IdsClaimsMarked, c->tok_slot.as<int>(), T, n, c->x_ecnt.as<unsigned int>()));
   stage_end(c);
   stage_begin(c, "node_filter");
   AMGCHK(c->x_first_all.ensure((size_t)(n + 2) * sizeof(unsigned int)));
@@ -1174,7 +1174,7 @@ int bx_node_count(amg_ctx* c, bool tag) {
   const long long S = c->x_nspace;
   AMGCHK(c->x_ncnt.ensure((size_t)(S + 2) * sizeof(unsigned int)));
   if (tag) AMGCHK(c->x_ftag.ensure((size_t)(S + 2) * sizeof(int)));
-  AMGCHK(count_ids(c, c->tok_slot.as<int>(), T, nullptr, S, c->x_ncnt.as<unsigned int>(), 4));
+  AMGCHK(count_ids(c, CountNodes, IdsClaimsMarked, c->tok_slot.as<int>(), T, S, c->x_ncnt.as<unsigned int>()));
   if (S > 0 && D > 0)
     hipLaunchKernelGGL(k_x_cov_from_claims, dim3(nblk(S, 256)), dim3(256), 0, c->stream,
                        c->x_ncnt.as<unsigned int>(), c->x_first.as<unsigned int>(), c->x_final.as<int>(), S,
@@ -1252,7 +1252,7 @@ int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov, bool nodes_counted) {
   // edge-class coverage per claim
   stage_begin(c, "edge_count");
   AMGCHK(c->x_ecnt.ensure((size_t)(P + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, c->tok_pair.as<int>(), T, nullptr, P, c->x_ecnt.as<unsigned int>(), 5));
+  AMGCHK(count_ids(c, CountEdgeClasses, IdsClaimsMarked, c->tok_pair.as<int>(), T, P, c->x_ecnt.as<unsigned int>()));
   stage_end(c);
   if (min_edge_cov > 1 && P > 0) {  // filter_graph's edge threshold (:531-535)
     hipStream_t st = c->stream;

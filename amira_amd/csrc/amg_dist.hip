@@ -601,7 +601,7 @@ extern "C" int amg_dist_merge_begin(amg_ctx* c, int32_t k, uint32_t min_node_cov
   // the reads are what a correction left of the reads of the merged graph still held (amg_adopt_corrected), same k, plain
   // build: the ranks first find out whether that graph's live part will do (S_DV_*; AMG_NO_DERIVE=1: A/B + test switch)
   const bool candidate = c->dist_candidate && c->dist_mode && c->world == d->world && k == c->k && d->mn == 1 && d->me == 1 &&
-                         !getenv("AMG_NO_DERIVE");
+                         !getenv("AMG_NO_DERIVE");  // (not c->sw: this build reads its switches later, in nodes_local)
   if (!candidate) c->dist_candidate = c->derive_ready = false;
   d->state = candidate ? S_DV_LOCAL : S_LOCAL;
   return AMG_OK;

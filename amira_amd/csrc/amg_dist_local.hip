@@ -278,7 +278,7 @@ static int nodes_local_x(amg_ctx* c, DistState* d, unsigned long long key_mask) 
   // local occurrence counts per claim, straight from the per-window claims
   stage_begin(c, "node_count");
   AMGCHK(d->loc_cnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, c->tok_slot.as<int>(), T, nullptr, n, d->loc_cnt.as<unsigned int>(), 4));
+  AMGCHK(count_ids(c, CountNodes, IdsClaimsMarked, c->tok_slot.as<int>(), T, n, d->loc_cnt.as<unsigned int>()));
   stage_end(c);
   stage_begin(c, "merge_node_bucket");
   Bucketing b;
@@ -304,7 +304,7 @@ static int edges_local_x(amg_ctx* c, DistState* d) {
   const long long n = c->x_espace, T = c->n_tokens;  // (claim ids in use lie below n: see nodes_local_x)
   stage_begin(c, "edge_count");
   AMGCHK(d->loc_cnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, c->tok_pair.as<int>(), T, nullptr, n, d->loc_cnt.as<unsigned int>(), 5));
+  AMGCHK(count_ids(c, CountEdgeClasses, IdsClaimsMarked, c->tok_pair.as<int>(), T, n, d->loc_cnt.as<unsigned int>()));
   stage_end(c);
   stage_begin(c, "merge_edge_bucket");
   Bucketing b;
@@ -332,9 +332,9 @@ static int fp_records_local(amg_ctx* c, DistState* d, int kind) {
   AMGCHK(prim_sort_u64_u32(c, c->s1.as<unsigned long long>(), c->s2.as<unsigned long long>(),
                            c->s3.as<unsigned int>(), c->s4.as<unsigned int>(), (size_t)n, ilog2_ceil(first_top) + 1));
   AMGCHK(d->loc_cnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  AMGCHK(bs_count_by_slot(c, kind ? c->tok_pair.as<int>() : c->tok_slot.as<int>(),
+  AMGCHK(bs_count_by_slot(c, kind ? CountEdgeClasses : CountNodes, kind ? c->tok_pair.as<int>() : c->tok_slot.as<int>(),
                           kind ? c->tok_pair.as<int>() : c->tok_node.as<int>(), c->n_tokens, tab,
-                          c->s4.as<unsigned int>(), n, d->loc_cnt.as<unsigned int>(), kind));
+                          c->s4.as<unsigned int>(), n, d->loc_cnt.as<unsigned int>()));
   Bucketing b;
   AMGCHK(bucketing(d, n, &b));
   // keep the compaction list in first-seen order (s2 / s4: the sort's output): the later sorts use the generic scratch

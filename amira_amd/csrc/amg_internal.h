@@ -133,7 +133,7 @@ struct BuildSwitches {
   long long head_tiles = 0;     // head_tiles()'s rule
   int claim_shards = -1;        // AMG_CLAIM_SHARDS: 0 / 1 claims from the shard counters never / always, -1 (unset) by size
   bool tight_bits = false;      // AMG_X_TIGHT_BITS: as few bits per token as the vocabulary needs, not 16
-  bool key_fp = false;          // AMG_KEY_MODE=fp: the 32-byte fingerprint path of amg_build.hip
+  bool key_fp = false;          // AMG_KEY_MODE=fp: the 32-byte fingerprint path of amg_build_fp.hip
   bool node_buckets = true;     // AMG_NODE_BUCKETS=0: hashed node slots only (k_nodes_v)
   bool generic_k = false;       // AMG_X_GENERIC_K: the node kernel with k at run time for every k
   bool rank_sort = false;       // AMG_X_RANK_SORT: radix sort instead of the bitmap ranking where both apply
@@ -142,6 +142,8 @@ struct BuildSwitches {
   bool no_derive = false;       // AMG_NO_DERIVE: never derive the rebuild from the graph at hand
   int weak_fp = 0;              // AMG_TEST_WEAK_FP: attempts that use a 12-bit fingerprint
   bool count_inline = false;    // AMG_COUNT_INLINE=1: one global atomic per window
+  int count_list_seg = 1 << 30;  // AMG_COUNT_LIST_SEG: ids per list segment of a counting sweep (count_ids clamps it)
+  bool count_debug = false;     // AMG_COUNT_DEBUG: count_ids prints the state of its sweeps (synchronises)
 };
 BuildSwitches read_build_switches();  // amg_build.hip
 
@@ -418,21 +420,36 @@ int derive_local(amg_ctx* c, int k, long long own_lo, long long own_tokens, cons
                  long long* bounds_host, long long* D2_out, long long* P2_out, bool* ok);
 int derive_commit(amg_ctx* c, long long D2, long long P2);
 
-// build stages (amg_build.hip), shared with the multi-GPU path (amg_dist.hip)
+// the build driver and the stages every key scheme shares (amg_build.hip), also used by the multi-GPU path (amg_dist*.hip)
 uint64_t pow2_at_least(uint64_t x);
 uint64_t slots_for(uint64_t n_keys);
 void bs_size_tables(amg_ctx* c);
 int grow_after_overflow(amg_ctx* c, Overflow cause);  // the next attempt's tables / seed; counts the retry
 int bs_read_stats(amg_ctx* c, int k, const ClearList* also = nullptr);
-int bs_nodes_pass(amg_ctx* c, int k, Overflow* which);
 int bs_alloc_nodes(amg_ctx* c, long long D);
+int bs_alloc_pairs(amg_ctx* c, long long P);
+int bs_finish_from_pairs(amg_ctx* c);
+// the 32-byte-slot fingerprint path (amg_build_fp.hip)
+int bs_nodes_pass(amg_ctx* c, int k, Overflow* which);
 int bs_nodes_rank_local(amg_ctx* c);
 int bs_edges_pass(amg_ctx* c, Overflow* which);
-int bs_alloc_pairs(amg_ctx* c, long long P);
 int bs_pairs_from_local(amg_ctx* c);
-int bs_finish_from_pairs(amg_ctx* c);
+// the views of a built graph that are made on first use (amg_adjacency.hip)
 int ensure_components(amg_ctx* c);
 int ensure_adjacency(amg_ctx* c);
+// deferred counting (amg_count.hip)
+enum CountKind { CountNodes = 0, CountEdgeClasses = 1 };  // what is counted: index of the state block, the hint, cnt_sweeps[]
+enum CountIds {
+  IdsPlain,         // dense ids (or, with a gather table, its slots), -1 = none
+  IdsClaimsMarked,  // claims as an exact-key table pass wrote them: flag bits on top, AMG_MADE_FLAG on the occurrence that
+                    // created the key — that one is skipped and every counter starts at 1
+};
+int count_ids(amg_ctx* c, CountKind what, CountIds form, int* ids, long long n, long long n_ids, unsigned int* out,
+              const Slot* gather_tab = nullptr);
+#define COUNT_LEARN_WORDS 8  // done flags that count_learn_add asks for
+bool count_learn_add(amg_ctx* c, FetchList* l);
+void count_learn_take(amg_ctx* c, const unsigned long long* done /*[COUNT_LEARN_WORDS]*/);
+// the exact-key path (amg_build_x.hip)
 bool bx_applicable(const amg_ctx* c, int k);
 bool bx_fits(const amg_ctx* c, int k);
 bool bx_tuple_fits(const amg_ctx* c, int k);
@@ -445,17 +462,11 @@ int bx_flag_dead_reads(amg_ctx* c);
 int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone = false, bool sharded = false, bool rank_follows = true);
 int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov = 0, bool nodes_counted = false);
 int bx_node_count(amg_ctx* c, bool tag);
-int count_ids(amg_ctx* c, int* ids, long long n, const Slot* gather_tab, long long n_ids,
-              unsigned int* out, int kind, const int* remap = nullptr);
-// counts of remap[claim] over per-window node claims (claim | AMG_LAST_FLAG, -1 none); the array is
-// rewritten to the remapped ids
-int count_ids_remap(amg_ctx* c, int* claims, long long n, const int* remap, long long n_ids, unsigned int* out,
-                    int edges);
 int bx_bits(const amg_ctx* c, int k);
 int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal);
 int bx_components_from_claims(amg_ctx* c);
-int bs_count_by_slot(amg_ctx* c, const int* slots, int* ids_scratch, long long n, Slot* tab,
-                     const unsigned int* slot_sorted, long long n_ids, unsigned int* out, int kind);
+int bs_count_by_slot(amg_ctx* c, CountKind what, const int* slots, int* ids_scratch, long long n, Slot* tab,
+                     const unsigned int* slot_sorted, long long n_ids, unsigned int* out);  // amg_build_fp.hip
 
 // entry points that need a built graph start with this
 #define NEED_BUILT(c)                                                     \

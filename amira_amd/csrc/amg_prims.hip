@@ -1,8 +1,8 @@
 // amg_prims.hip — library primitives (radix sort) behind a narrow interface (prefix sums: amg_scan.hip).
 // rocPRIM does the generic sorting of SMALL arrays (distinct nodes, edge
 // classes); every gene-mer-sized kernel (window extraction, hashing, table upsert,
-// compaction, masking, threading, matching) is hand-written in amg_build.hip /
-// amg_filter.hip.  Kept in its own translation unit because it dominates compile time.
+// compaction, masking, threading, matching) is hand-written in amg_build_x.hip /
+// amg_build_fp.hip / amg_filter.hip.  Kept in its own translation unit because it dominates compile time.
 #include "amg_internal.h"
 
 #include <rocprim/rocprim.hpp>
