@@ -133,6 +133,7 @@ def _load():
         "amg_last_timings": (C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
         "amg_set_timing": (C.c_int, [P, C.c_int]),
         "amg_scan_probe": (C.c_int, [P, C.c_int, P, I64, P, P]),
+        "amg_count_probe": (C.c_int, [P, C.c_int, C.c_int, P, I64, I64, P, I64, C.c_int, C.c_int, P, P]),
         "amg_correct_routes": (C.c_int, [P, P, I32]),
     }
     for name, (res, args) in sig.items():

@@ -188,14 +188,17 @@ int count_ids(amg_ctx* c, CountKind what, CountIds form, int* ids, long long n, 
   CountState* cs = c->cnt_state.as<CountState>();
   CountSweeps* state = &cs->sweeps[what];
   CountHint* hint = &cs->hint[what];
-  cl.add(state, sizeof(CountSweeps));
-  if (fresh) cl.add(cs->hint, sizeof(cs->hint));
+  // (fresh: both kinds' sweeps and both hints — the done flags of the kind that is not counted now are read when a
+  // build learns, and nothing has written them yet on a new context)
+  if (fresh) cl.add(cs, sizeof(CountState));
+  else cl.add(state, sizeof(CountSweeps));
   AMGCHK(c->cnt_list.ensure((size_t)(COUNT_LIST_HEAD + COUNT_MAX_BLOCKS * COUNT_LIST_SEG) * sizeof(unsigned int)));
   unsigned int* list = c->cnt_list.as<unsigned int>();
   cl.add(list, COUNT_LIST_HEAD * sizeof(unsigned int));
   // AMG_COUNT_LIST_SEG: test switch (a small segment runs over: the second launch sweeps)
   const unsigned int seg_cap = (unsigned int)std::min(std::max(c->sw.count_list_seg, 0), COUNT_LIST_SEG);
   AMGCHK(clear_many(c, cl));
+  c->cnt_launched[0] = c->cnt_launched[1] = 0;
   if (n <= 0 || n_ids <= 0) return AMG_OK;
   long long ranges = (n_ids + HOT_IDS - 1) / HOT_IDS;
   if (ranges > COUNT_MAX_SWEEPS) ranges = COUNT_MAX_SWEEPS;
@@ -206,6 +209,8 @@ int count_ids(amg_ctx* c, CountKind what, CountIds form, int* ids, long long n, 
   // block at least twice that many ids to count (small inputs: fewer blocks, not a shorter sweep)
   long long want_blocks = (n + 2 * HOT_IDS - 1) / (2 * HOT_IDS);
   unsigned int blocks = (unsigned int)(want_blocks < 1 ? 1 : (want_blocks < COUNT_MAX_BLOCKS ? want_blocks : COUNT_MAX_BLOCKS));
+  c->cnt_launched[0] = (int)ranges;
+  c->cnt_launched[1] = (int)blocks;
   for (long long r = 0; r < ranges; ++r) {
     const long long lo = r * HOT_IDS;
     const int last = (r == ranges - 1) ? 1 : 0;
@@ -246,4 +251,87 @@ void count_learn_take(amg_ctx* c, const unsigned long long* done) {
       if (done[s * COUNT_MAX_SWEEPS + q]) used = q + 1;
     c->cnt_sweeps[s] = used;
   }
+}
+
+// ------------------------------------------------------------------ amg_count_probe (tests: one count on host arrays)
+extern "C" int amg_count_probe(amg_ctx* c, int kind, int form, int32_t* ids, int64_t n, int64_t n_ids, const int32_t* tab_ids,
+                               int64_t n_slots, int misalign, int flags, uint32_t* counts, int64_t* state) {
+  if (!c || (kind != CountNodes && kind != CountEdgeClasses) || form < 0 || form > 2 || n < 0 || n_ids < 0 ||
+      n_ids >= (1ll << 29) || (n > 0 && !ids) || misalign < 0 || misalign > 3 || !counts || !state ||
+      (form == 2 && (n_slots < 0 || (n_slots > 0 && !tab_ids))))
+    return amg_fail(AMG_E_ARG, "count_probe: bad arguments");
+  // the sweeps index their counters by what the array holds: nothing out of range goes to the device
+  for (int64_t i = 0; i < n; ++i) {
+    long long id = ids[i];
+    if (form == 1 && id != -1) id = (long long)((unsigned int)ids[i] & ~AMG_FLAG_MASK);
+    if (form == 2 && id >= 0) {
+      if (id >= n_slots) return amg_fail(AMG_E_ARG, "count_probe: slot %lld at %lld beyond the table", id, (long long)i);
+      id = tab_ids[id];
+    }
+    if (id >= n_ids) return amg_fail(AMG_E_ARG, "count_probe: id %lld at %lld, n_ids %lld", id, (long long)i, (long long)n_ids);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const size_t guard = 64;  // words in front of and behind the id array, and behind the counts: 0xff before the call
+  const size_t ids_words = guard + (size_t)n + 4 + guard, cnt_words = (size_t)n_ids + 1 + guard;
+  const size_t tab_bytes = form == 2 ? ((size_t)n_slots + 1) * sizeof(Slot) : 0;
+  const size_t ids_cap = (ids_words * 4 + 255) & ~(size_t)255, cnt_cap = (cnt_words * 4 + 255) & ~(size_t)255;
+  char* d = nullptr;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&d), ids_cap + cnt_cap + tab_bytes));
+  int* dbuf = reinterpret_cast<int*>(d);
+  int* dids = dbuf + guard + misalign;  // (hipMalloc aligns to 256 bytes, the guard is 256 bytes)
+  unsigned int* dcnt = reinterpret_cast<unsigned int*>(d + ids_cap);
+  Slot* dtab = form == 2 ? reinterpret_cast<Slot*>(d + ids_cap + cnt_cap) : nullptr;
+  std::vector<unsigned int> back;
+  int rc = AMG_OK;
+  do {
+    if (hipMemset(d, 0xff, ids_cap + cnt_cap) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "count_probe: memset"); break; }
+    if (n && hipMemcpy(dids, ids, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "h2d"); break; }
+    if (form == 2) {
+      std::vector<Slot> tab((size_t)n_slots + 1);
+      memset(tab.data(), 0xff, tab.size() * sizeof(Slot));
+      for (int64_t i = 0; i < n_slots; ++i) tab[i].id = tab_ids[i];
+      if (hipMemcpy(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "h2d"); break; }
+    }
+    if (hipDeviceSynchronize() != hipSuccess) { rc = amg_fail(AMG_E_HIP, "count_probe: sync"); break; }
+    c->sw = read_build_switches();
+    if (flags & 1) c->cnt_hint_reset = true;  // what amg_set_reads does: the next count starts without hints
+    rc = count_ids(c, (CountKind)kind, form == 1 ? IdsClaimsMarked : IdsPlain, dids, n, n_ids, dcnt, dtab);
+    if (rc != AMG_OK) break;
+    if (flags & 2) {  // what a build's final read-back does
+      FetchList l;
+      unsigned long long v[COUNT_LEARN_WORDS] = {0};
+      if (count_learn_add(c, &l)) {
+        if ((rc = fetch(c, l, v)) != AMG_OK) break;
+        count_learn_take(c, v);
+      }
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "count_probe: stream"); break; }
+    CountSweeps h;
+    unsigned int lst[2];
+    if (hipMemcpy(&h, &c->cnt_state.as<CountState>()->sweeps[kind], sizeof(h), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(lst, c->cnt_list.p, sizeof(lst), hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = amg_fail(AMG_E_HIP, "d2h");
+      break;
+    }
+    back.resize(ids_words > cnt_words ? ids_words : cnt_words);
+    bool intact = true;
+    if (hipMemcpy(back.data(), dbuf, ids_words * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "d2h"); break; }
+    const size_t first = guard + (size_t)misalign;
+    for (size_t i = 0; i < ids_words; ++i)
+      if ((i < first || i >= first + (size_t)n) && back[i] != 0xffffffffu) intact = false;
+    if (n) memcpy(ids, back.data() + first, (size_t)n * 4);
+    if (hipMemcpy(back.data(), dcnt, cnt_words * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = amg_fail(AMG_E_HIP, "d2h"); break; }
+    for (size_t i = (size_t)n_ids + 1; i < cnt_words; ++i)
+      if (back[i] != 0xffffffffu) intact = false;
+    memcpy(counts, back.data(), ((size_t)n_ids + 1) * 4);
+    for (int q = 0; q < COUNT_MAX_SWEEPS; ++q) state[q] = (int64_t)h.beyond[q], state[4 + q] = (int64_t)h.done[q];
+    state[8] = lst[0];
+    state[9] = lst[1];
+    state[10] = c->cnt_launched[0];
+    state[11] = c->cnt_launched[1];
+    state[12] = c->cnt_sweeps[kind];
+    state[13] = intact ? 1 : 0;
+  } while (false);
+  (void)hipFree(d);
+  return rc;
 }

@@ -315,6 +315,7 @@ struct amg_ctx {
   bool cnt_hint_reset = false;
   DevBuf cnt_list;     // k_count_ids: what the first sweep of a count found beyond its range, while that is little
   int cnt_sweeps[2] = {4, 4};  // sweeps the last node / edge-class count made use of (count_ids launches no more)
+  int cnt_launched[2] = {0, 0};  // sweeps and workgroups per sweep of the last count_ids call (amg_count_probe)
 
   BuildSwitches sw;  // of the build in progress / the last one
   std::vector<StageTime> stages;

@@ -447,6 +447,22 @@ int amg_set_timing(amg_ctx* ctx, int on);
  *    cov (uint32), sdir, tdir (int8), alive (uint8) over 2n edges each. */
 int amg_scan_probe(amg_ctx* ctx, int kind, const void* in, int64_t n, int64_t* out, void* aux);
 
+/* ---- tests: one count of the coverage counting sweeps on host arrays ------------------------------
+ * counts[i] for i <= n_ids = what the engine's counting sweeps (amg_count.hip) make of ids[0 .. n), in the state the
+ * previous counts on this ctx left behind.  kind: 0 nodes, 1 edge classes (which hint, which learnt number of sweeps).
+ * form 0: plain ids, negative = none.  1: marked claims (-1 = none, bit 31 = last-of-read flag, ignored; bit 30 on the
+ * occurrence that made the id — exactly one per id present — which is skipped while every counter starts at 1).
+ * 2: ids holds slots of a table whose slot s has id tab_ids[s] (n_slots of them); ids is rewritten to those ids.
+ * ids comes back as the call left it.  misalign: 0 .. 3 ints between a 16-byte boundary and the device copy of ids.
+ * flags: 1 = forget the hints first (as amg_set_reads does), 2 = learn the number of sweeps afterwards (as the last
+ * read-back of a build does).  AMG_COUNT_LIST_SEG is read from the environment as a build reads it.
+ * state[16]: [0..3] ids every sweep found beyond its range, [4..7] sweep finished the count, [8] a list segment ran
+ * over, [9] the first sweep listed, [10] sweeps launched, [11] workgroups per sweep, [12] the learnt number of sweeps
+ * of this kind after the call, [13] 1 = the 0xff guard words around the device copy of ids and behind counts[n_ids]
+ * are intact.  An id (or slot) outside its range is refused with AMG_E_ARG before anything runs. */
+int amg_count_probe(amg_ctx* ctx, int kind, int form, int32_t* ids, int64_t n, int64_t n_ids, const int32_t* tab_ids,
+                    int64_t n_slots, int misalign, int flags, uint32_t* counts, int64_t* state);
+
 /* ---- tests: which read took which route through the last amg_correct_reads call ----------------------
  * With AMG_CORR_ROUTES=1 in the environment of an amg_correct_reads call, small tally kernels run behind its steps
  * (without it the call launches and reads back what it always did).  amg_correct_routes copies the tallies of the

@@ -159,3 +159,56 @@ def test_hashed_edge_region_overflow_is_rebuilt():
     finally:
         eng.close()
         orc.close()
+
+
+@pytest.mark.parametrize("key_mode", ["default", "fp"])
+def test_counting_sweeps_beyond_four_id_ranges_over_rebuilds(monkeypatch, key_mode):
+    """20 000 reads of 12 random genes from a 50 000-gene vocabulary: about 200 000 nearly distinct windows, so node and
+    edge-class ids fill more than the four ranges of 39 936 ids that the counting sweeps keep in LDS and nothing is hot
+    (tests/test_gpu_count.py has the sweeps on their own).  Built at k = 3, 5, 7, 3 on one context — every count starts
+    from the hint and the number of sweeps the build before it left — in the default key mode (marked claims) and with
+    fingerprint keys (gathered slots); then a read set cut from a 60-gene genome on the same context, where a few low
+    ids take nearly every window and what the sweeps learnt from the first set must be forgotten.  Node tokens and
+    coverage, edge endpoints and coverage against the sequential C oracle."""
+    import token_oracle
+    from amira_amd import Engine
+    if key_mode == "fp":
+        monkeypatch.setenv("AMG_KEY_MODE", "fp")
+    rng = np.random.default_rng(17)
+    N, L = 20000, 12
+
+    def as_tokens(genes, strands, V):
+        return np.where(strands == 1, V + genes, V - 1 - genes).astype(np.int32)
+
+    V1 = 50000
+    set1 = (as_tokens(rng.integers(0, V1, (N, L)), rng.integers(0, 2, (N, L)), V1).ravel(), 2 * V1)
+    # reads along a circular genome of 60 genes, either strand, 3 % of the genes replaced
+    V2 = 60
+    genome = as_tokens(rng.permutation(V2), rng.integers(0, 2, V2), V2)
+    rows = genome[(rng.integers(0, V2, N)[:, None] + np.arange(L)[None, :]) % V2]
+    flip = rng.random(N) < 0.5
+    rows[flip] = 2 * V2 - 1 - rows[flip][:, ::-1]
+    wrong = rng.random((N, L)) < 0.03
+    rows[wrong] = rng.integers(0, 2 * V2, int(wrong.sum()))
+    set2 = (rows.astype(np.int32).ravel(), 2 * V2)
+    offs = np.arange(0, (N + 1) * L, L, dtype=np.int64)
+    eng = Engine(0)
+    try:
+        for which, (toks, two_v) in enumerate((set1, set2)):
+            eng.set_reads(toks, offs, two_v)
+            for k in (3, 5, 7, 3):
+                eng.build(k)
+                want = token_oracle.build(toks, offs, k, two_v)
+                c = eng.counts()
+                nodes, edges = eng.nodes(), eng.edges()
+                assert c["n_windows"] == want["n_windows"] == N * (L - k + 1)
+                if which == 0:
+                    assert c["n_nodes"] > (4 if k < 7 else 3) * 39936 - 2000, (k, c["n_nodes"])
+                else:
+                    assert c["n_nodes"] < 39936 and nodes["coverage"][:V2].sum() > c["n_windows"] // 2
+                assert np.array_equal(nodes["tokens"], want["tokens"]), (which, k)
+                assert np.array_equal(nodes["coverage"], want["coverage"]), (which, k)
+                for a, b in (("src", "src"), ("tgt", "tgt"), ("sdir", "sdir"), ("tdir", "tdir"), ("coverage", "ecov")):
+                    assert np.array_equal(edges[a], want[b]), (which, k, a)
+    finally:
+        eng.close()
