@@ -17,6 +17,7 @@
 // What decides with these numbers (which path of a pair is the better one, which reads are rewritten) stays host-side
 // orchestration over a handful of paths, as in the reference (amira_amd/bubble_popping.py).
 #include "amg_kmer.h"
+#include "amg_wave_dfs.h"
 
 #include <algorithm>
 
@@ -80,11 +81,56 @@ __device__ __forceinline__ int bj_edges_between(const GView& g, int a, int b) {
 #define BJ_BUDGET 2ull   // a search was abandoned
 #define BJ_STEPS (1ull << 24)
 
-// One WAVE per start junction, the search run cooperatively as in amg_correct_gapped.hip (dfs_paths_wave): stack level d lives in
-// lane d.  A node entered at depth d >= 1 with L = d + 1 <= distance nodes on the path that is a junction on the side the
+// One WAVE per start junction, the search run cooperatively (wave_dfs, amg_wave_dfs.h: stack level d lives in lane d).
+// A node entered at depth d >= 1 with L = d + 1 <= distance nodes on the path that is a junction on the side the
 // path arrives at is a record {stop junction, the L nodes and directions}; EMIT = false counts records and path nodes,
 // EMIT = true writes them behind the start's share of the pools — in search order, which is the order the reference's
 // per-stop searches return them in.  Nodes are expanded while L < distance (a longer path ends nowhere: :2305).
+template <bool EMIT>
+struct BjVisit {
+  const GView& g;
+  const unsigned char* jflag;
+  const long long *jpos, *rec_base, *int_base;  // (the bases and what follows: EMIT only)
+  int* rec_stop;
+  long long* rec_off;
+  int* pool_node;
+  signed char* pool_dir;
+  long long j;
+  int distance, lane;
+  long long n_rec, n_int;
+  unsigned long long steps, bad;
+  __device__ __forceinline__ int enter(int d, int L, int cur_node, int cur_dir, int my_node, int my_dir) {
+    if (++steps > BJ_STEPS) {
+      bad |= BJ_BUDGET;
+      return WD_ABORT;
+    }
+    if (d >= 1 && L <= distance && (jflag[2ll * cur_node] | jflag[2ll * cur_node + 1])) {
+      // the reference asks for THE edge between the last two nodes of every path that ends at a junction node
+      // (:2086, :1515-1523) and fails when there are several
+      const int prev = __builtin_amdgcn_readlane(my_node, d - 1);
+      if (bj_edges_between(g, prev, cur_node) > 1 || bj_edges_between(g, cur_node, prev) > 1) bad |= BJ_MULTI;
+      // arriving with direction +1 is arriving through the node's backward side (:1523: -1 x the edge's target direction)
+      const long long arow = 2ll * cur_node + (cur_dir == 1 ? 1 : 0);
+      if (jflag[arow]) {
+        if (EMIT) {
+          const long long ri = rec_base[j] + n_rec, io = int_base[j] + n_int;
+          if (lane == 0) {
+            rec_stop[ri] = (int)jpos[arow];
+            rec_off[ri] = io;
+          }
+          if (lane < L) {
+            pool_node[io + lane] = my_node;
+            pool_dir[io + lane] = (signed char)my_dir;
+          }
+        }
+        ++n_rec;
+        n_int += L;
+      }
+    }
+    return L >= distance ? WD_RETREAT : WD_EXPAND;
+  }
+};
+
 template <bool EMIT>
 __global__ __launch_bounds__(64) void k_bj_dfs(GView g, const int* __restrict__ jrows, long long J,
                                                const unsigned char* __restrict__ jflag, const long long* __restrict__ jpos,
@@ -97,88 +143,14 @@ __global__ __launch_bounds__(64) void k_bj_dfs(GView g, const int* __restrict__ 
   if (j >= J) return;
   const int lane = threadIdx.x;
   const int row0 = jrows[j];
-  int my_node = 0, my_dir = 0, my_cur = 0, my_lim = 0, my_off = 0;
-  if (lane == 0) {
-    my_node = row0 >> 1;
-    my_dir = (row0 & 1) ? -1 : 1;
-  }
-  int depth = 0;
-  bool entering = true;
-  long long n_rec = 0, n_int = 0;
-  unsigned long long steps = 0, bad = 0;
-  while (depth >= 0) {
-    const int d = __builtin_amdgcn_readfirstlane(depth);
-    if (entering) {
-      entering = false;
-      if (++steps > BJ_STEPS) {
-        bad |= BJ_BUDGET;
-        break;
-      }
-      const int L = d + 1;
-      const int cur_node = __builtin_amdgcn_readlane(my_node, d);
-      const int cur_dir = __builtin_amdgcn_readlane(my_dir, d);
-      if (d >= 1 && L <= distance && (jflag[2ll * cur_node] | jflag[2ll * cur_node + 1])) {
-        // the reference asks for THE edge between the last two nodes of every path that ends at a junction node
-        // (:2086, :1515-1523) and fails when there are several
-        const int prev = __builtin_amdgcn_readlane(my_node, d - 1);
-        if (bj_edges_between(g, prev, cur_node) > 1 || bj_edges_between(g, cur_node, prev) > 1) bad |= BJ_MULTI;
-        // arriving with direction +1 is arriving through the node's backward side (:1523: -1 x the edge's target direction)
-        const long long arow = 2ll * cur_node + (cur_dir == 1 ? 1 : 0);
-        if (jflag[arow]) {
-          if (EMIT) {
-            const long long ri = rec_base[j] + n_rec, io = int_base[j] + n_int;
-            if (lane == 0) {
-              rec_stop[ri] = (int)jpos[arow];
-              rec_off[ri] = io;
-            }
-            if (lane < L) {
-              pool_node[io + lane] = my_node;
-              pool_dir[io + lane] = (signed char)my_dir;
-            }
-          }
-          ++n_rec;
-          n_int += L;
-        }
-      }
-      if (L >= distance) {
-        --depth;
-        continue;
-      }
-      const int4 rw = g.lrows[2ll * cur_node + (cur_dir == 1 ? 0 : 1)];  // uniform address
-      if (lane == d) {
-        my_cur = 0;
-        my_lim = rw.y;
-        my_off = rw.x;
-      }
-    }
-    int cur = __builtin_amdgcn_readlane(my_cur, d);
-    const int lim = __builtin_amdgcn_readlane(my_lim, d);
-    const int row_off = __builtin_amdgcn_readlane(my_off, d);
-    bool pushed = false;
-    while (cur < lim) {
-      const int2 ent = g.lent[row_off + cur];  // uniform address
-      ++cur;
-      const int t = __builtin_amdgcn_readfirstlane(ent.x);
-      const int td = __builtin_amdgcn_readfirstlane(ent.y);
-      if (__ballot(lane <= d && my_node == t) != 0ull) continue;  // no node twice on a path (:2327)
-      if (lane == d) my_cur = cur;
-      if (lane == d + 1) {
-        my_node = t;
-        my_dir = td;
-      }
-      ++depth;
-      entering = true;
-      pushed = true;
-      break;
-    }
-    if (!pushed) --depth;
-  }
+  BjVisit<EMIT> v{g, jflag, jpos, rec_base, int_base, rec_stop, rec_off, pool_node, pool_dir, j, distance, lane, 0, 0, 0, 0};
+  wave_dfs(g, row0 >> 1, (row0 & 1) ? -1 : 1, lane, v);
   if (lane == 0) {
     if (!EMIT) {
-      cnt_rec[j] = n_rec;
-      cnt_int[j] = n_int;
+      cnt_rec[j] = v.n_rec;
+      cnt_int[j] = v.n_int;
     }
-    if (bad) atomicOr(flags, bad);
+    if (v.bad) atomicOr(flags, v.bad);
   }
 }
 

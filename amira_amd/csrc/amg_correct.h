@@ -78,6 +78,20 @@ struct __attribute__((aligned(16))) GapRec {
   long long pad;
 };
 
+// The None runs of a read with <= 64 windows, read off its live-window mask lv (start, end: its first and last live
+// window).  A run ends at window i when i is not live and i + 1 is, start <= i < end (identify_path_terminals
+// :1375-1386; k_corr_classify counts the same bits); the runs are numbered by ascending end bit.
+__device__ __forceinline__ unsigned long long gap_run_ends(unsigned long long lv, int start, int end) {
+  const unsigned long long inside =
+      (end >= 63 ? ~0ull : ((1ull << (end + 1)) - 1ull)) & ~((1ull << (start & 63)) - 1ull);
+  return ~lv & inside & (lv >> 1);
+}
+// the run that ends at window i lies between the live windows ps (the last one before i) and pe
+__device__ __forceinline__ void gap_run_terminals(unsigned long long lv, int i, int& ps, int& pe) {
+  ps = 63 - __clzll((long long)(lv & ((1ull << i) - 1ull)));
+  pe = i + 1;
+}
+
 struct GapArgs {
   CorrArgs a;
   GView g;

@@ -1,7 +1,16 @@
 // amg_correct_gapped.hip — re-threading of the reads with None runs (stage correct_gapped of amg_correct_reads;
 // reference construct_graph.py:1166-1203, 1297-1310, 1331-1386, 2292-2342): the bounded path search, the path memo
 // and the three gapped kernels, with the host function that runs them.  (Pipeline: amg_correct.hip.)
+//   k_corr_classify                      (amg_correct.hip's classify step: see below why it is compiled here)
+//   dfs_paths, k_corr_gapped             the general kernel: a thread per read, its search stack in private arrays
+//   dfs_paths_wave                       the re-threading's visitor on the wave-cooperative search (amg_wave_dfs.h)
+//   k_gap_queries, k_gap_dfs             the path memo: every distinct question of the None runs answered once
+//   k_corr_gapped_lean                   sixteen lanes per read: the reads whose every question has one answer
+//   gf_* steps, gapped_fast_read, k_corr_gapped_fast   a wave per read, staged in LDS (GfLds)
+//   gap_memo, corr_gapped                the host side
+// (The None runs of a live-window mask: gap_run_ends / gap_run_terminals in amg_correct.h.)
 #include "amg_correct.h"
+#include "amg_wave_dfs.h"
 
 // ---- classification.  The kernel belongs to amg_correct.hip's classify step and is launched from here only because
 // of what the compiler does with it: the device library's 64-bit count-leading-zeros helper is optimised differently
@@ -236,6 +245,13 @@ struct GapIter {
   }
 };
 
+// the rule that ranks candidates: strictly more shared genes, or equal and strictly higher mean coverage (:1301-1308;
+// csum / n against best_sum / best_len by exact cross-multiplication = the order of statistics.mean)
+__device__ __forceinline__ bool cand_better(int shared, unsigned long long csum, int n, int best_shared,
+                                            unsigned long long best_sum, unsigned long long best_len) {
+  return shared > best_shared || (shared == best_shared && csum * best_len > best_sum * (unsigned long long)n);
+}
+
 // build candidate `combo` (mixed radix over the gaps' path choices) into (out_node, out_dir);
 // returns its node count.  paths of gap q start at pool[gap_off[q]] as [len, nodes, dirs] records.
 __device__ int build_candidate(const GapArgs& A, long long t0, int start, int end, const int* rec,
@@ -368,10 +384,7 @@ __global__ __launch_bounds__(64) void k_corr_gapped(GapArgs A) {
         for (int q = 0; q < L0 && !hit; ++q) hit = (a.tokens[t0 + q] == tk);
         shared += hit ? 1 : 0;
       }
-      // strictly more shared genes, or equal and strictly higher mean coverage (:1301-1308)
-      bool better = shared > best_shared ||
-                    (shared == best_shared && csum * best_len > best_sum * (unsigned long long)n);
-      if (better) {
+      if (cand_better(shared, csum, n, best_shared, best_sum, best_len)) {
         best_shared = shared;
         best_sum = csum;
         best_len = (unsigned long long)n;
@@ -388,100 +401,50 @@ __global__ __launch_bounds__(64) void k_corr_gapped(GapArgs A) {
 // general one-thread-per-read kernel above; results are identical by construction (same
 // DFS order, same product order, same comparisons).  (Capacities: GF_* in amg_correct.h.)
 
-// DFS of one None run, executed COOPERATIVELY by the whole wave: control flow is uniform,
-// stack level d lives in the registers of lane d (node, direction, row cursor), levels are
-// read with v_readlane, the "already on the path" test is one ballot, and an accepted path is
-// written to the pool by lanes 0..len-1 at once.  (A one-lane DFS with its stack in LDS or
-// scratch spends its time in dependent LDS/scratch round trips.)
-// Emits [run, len, nodes, dirs] records; returns the number of paths, -1 on pool overflow.
-__device__ int dfs_paths_wave(const GView& g, int s, int sdir, int e, int distance, int run, int* pool,
-                              int* used, int lane) {
-  int my_node = 0, my_dir = 0, my_cur = 0, my_lim = 0, my_off = 0;
-  int depth = 0, n_paths = 0;
-  bool overflow = false;
-  if (lane == 0) {
-    my_node = s;
-    my_dir = sdir;
-  }
-  bool entering = true;
-  int2 first_ent = make_int2(-1, 0);
-  while (depth >= 0) {
-    const int d = __builtin_amdgcn_readfirstlane(depth);
-    if (entering) {
-      const int L = d + 1;
-      const int cur_node = __builtin_amdgcn_readlane(my_node, d);
-      if (cur_node == e && L <= distance) {
-        const int off = *used;
-        if (off + 2 + 2 * L <= GF_POOL) {
-          if (lane == 0) {
-            pool[off] = run;
-            pool[off + 1] = L;
-          }
-          if (lane < L) {
-            pool[off + 2 + lane] = my_node;
-            pool[off + 2 + L + lane] = my_dir;
-          }
-        } else {
-          overflow = true;
+// The paths of one None run, found by the whole wave (wave_dfs, amg_wave_dfs.h): a path is accepted when it reaches
+// `e` with <= distance nodes and written to the LDS pool by lanes 0..len-1 at once, as a [run, len, nodes, dirs] record.
+struct GapVisit {
+  int e, distance, run, lane;
+  int *pool, *used;
+  int n_paths;
+  bool overflow;
+  __device__ __forceinline__ int enter(int, int L, int cur_node, int, int my_node, int my_dir) {
+    if (cur_node == e && L <= distance) {
+      const int off = *used;
+      if (off + 2 + 2 * L <= GF_POOL) {
+        if (lane == 0) {
+          pool[off] = run;
+          pool[off + 1] = L;
         }
-        wave_sync();
-        if (lane == 0) *used = off + 2 + 2 * L;
-        wave_sync();
-        ++n_paths;
-        --depth;
-        entering = false;
-        first_ent.x = -1;
-        continue;
+        if (lane < L) {
+          pool[off + 2 + lane] = my_node;
+          pool[off + 2 + L + lane] = my_dir;
+        }
+      } else {
+        overflow = true;
       }
-      if (L - 1 > distance) {
-        --depth;
-        entering = false;
-        first_ent.x = -1;
-        continue;
-      }
-      const int cur_dir = __builtin_amdgcn_readlane(my_dir, d);
-      const int4 rw = g.lrows[2ll * cur_node + (cur_dir == 1 ? 0 : 1)];  // uniform address
-      if (lane == d) {
-        my_cur = 0;
-        my_lim = rw.y;
-        my_off = rw.x;
-      }
-      first_ent = make_int2(rw.z, rw.w);
-      entering = false;
+      wave_sync();
+      if (lane == 0) *used = off + 2 + 2 * L;
+      wave_sync();
+      ++n_paths;
+      return WD_RETREAT;
     }
-    int c = __builtin_amdgcn_readlane(my_cur, d);
-    const int lim = __builtin_amdgcn_readlane(my_lim, d);
-    const int row_off = __builtin_amdgcn_readlane(my_off, d);
-    bool pushed = false;
-    while (c < lim) {
-      int2 ent = first_ent;
-      if (!(c == 0 && first_ent.x >= 0)) ent = g.lent[row_off + c];  // uniform address
-      ++c;
-      const int t = __builtin_amdgcn_readfirstlane(ent.x);
-      const int td = __builtin_amdgcn_readfirstlane(ent.y);
-      if (__ballot(lane <= d && my_node == t) != 0ull) continue;  // no node twice on a path
-      if (lane == d) my_cur = c;
-      if (lane == d + 1) {
-        my_node = t;
-        my_dir = td;
-      }
-      ++depth;
-      entering = true;
-      pushed = true;
-      break;
-    }
-    if (!pushed) {
-      --depth;
-      first_ent.x = -1;  // back in an older row: its first entry was consumed long ago
-    }
+    return L - 1 > distance ? WD_RETREAT : WD_EXPAND;
   }
-  return overflow ? -1 : n_paths;
+};
+
+// returns the number of paths, -1 on pool overflow
+__device__ __forceinline__ int dfs_paths_wave(const GView& g, int s, int sdir, int e, int distance, int run, int* pool,
+                                              int* used, int lane) {
+  GapVisit v{e, distance, run, lane, pool, used, 0, false};
+  wave_dfs(g, s, sdir, lane, v);
+  return v.overflow ? -1 : v.n_paths;
 }
 
 // ---- path memo.  k_gap_queries: one LANE per re-threaded read walks the read's None runs on its live-window mask
 // (k_corr_classify kept it), looks up the three node words of each run and enters the question (start node, start
 // direction, end node) into an open-addressing table; the slot index is the question's id, the lane that created
-// the slot lists it.  k_gap_dfs answers every listed question once (the wave-cooperative search below, result copied
+// the slot lists it.  k_gap_dfs answers every listed question once (the wave-cooperative search, dfs_paths_wave; result copied
 // to a global pool); k_corr_gapped_fast copies answers instead of searching.  Reads with more than 64 windows or
 // more than GF_MAXGAP runs take no part (gq[0] = -1: they search for themselves, as before).
 __device__ __forceinline__ unsigned long long gap_query_key(int s, int sdir, int e) {
@@ -509,20 +472,15 @@ __global__ __launch_bounds__(256) void k_gap_queries(const GapRec* __restrict__ 
     int* my = gq + gi * GF_MAXGAP;
     const int nwin = q.L0 - k + 1;
     const unsigned long long lv = q.mask;
-    // a None run ends at window i when i is not live and i + 1 is, first <= i < last (k_corr_classify's `runs`)
-    const int first = q.start, last = q.end;
-    const unsigned long long inside =
-        (last >= 63 ? ~0ull : ((1ull << (last + 1)) - 1ull)) & ~((1ull << (first & 63)) - 1ull);
-    unsigned long long ends = ~lv & inside & (lv >> 1);
+    unsigned long long ends = gap_run_ends(lv, q.start, q.end);
     if (nwin > 64 || lv == 0ull || __popcll(ends) > GF_MAXGAP) {
       my[0] = -1;
     } else {
       int j = 0;
       while (ends) {
-        const int i = __ffsll((long long)ends) - 1;
+        int ps, pe;
+        gap_run_terminals(lv, __ffsll((long long)ends) - 1, ps, pe);
         ends &= ends - 1ull;
-        const int ps = 63 - __clzll((long long)(lv & ((1ull << i) - 1ull)));  // the live window before the run
-        const int pe = i + 1;
         const unsigned long long key = gap_query_key(tok_node[q.t0 + ps], (int)tok_dir[q.t0 + ps], tok_node[q.t0 + pe]);
         unsigned int idx = (unsigned int)mix64(key) & qmask;
         int slot = -1;
@@ -648,12 +606,9 @@ __global__ __launch_bounds__(GL_THREADS) void k_corr_gapped_lean(GapArgs A, cons
   const unsigned long long lv = rec.mask;
   const int nwin = rec.L0 - k + 1;
   bool ok = have && nwin <= 64 && lv != 0ull;
-  // the read's None runs as k_gap_queries numbered them: run q ends at the q-th window that is not live while the
-  // next one is (identify_path_terminals :1375-1386)
+  // the read's None runs as k_gap_queries numbered them: run q ends at the q-th set bit of gap_run_ends
   const int first = rec.start, last = rec.end;
-  const unsigned long long inside =
-      (last >= 63 ? ~0ull : ((1ull << (last + 1)) - 1ull)) & ~((1ull << (first & 63)) - 1ull);
-  unsigned long long ends = ok ? (~lv & inside & (lv >> 1)) : 0ull;
+  unsigned long long ends = ok ? gap_run_ends(lv, first, last) : 0ull;
   const int n_gaps = __popcll(ends);
   ok = ok && n_gaps >= 1 && n_gaps <= GF_MAXGAP;
   // (k_gap_queries left gq[0] = -1 on a read it did not enter)
@@ -669,9 +624,7 @@ __global__ __launch_bounds__(GL_THREADS) void k_corr_gapped_lean(GapArgs A, cons
   if (mine) {
     unsigned long long e = ends;
     for (int j = 0; j < l16; ++j) e &= e - 1ull;
-    const int i = __ffsll((long long)e) - 1;
-    ps = 63 - __clzll((long long)(lv & ((1ull << i) - 1ull)));
-    pe = i + 1;
+    gap_run_terminals(lv, __ffsll((long long)e) - 1, ps, pe);
   }
   const int len = (mine && res.y >= 4) ? (res.y - 2) >> 1 : 0;  // one record [run, len, nodes, dirs]
   const bool good = !mine || (slot >= 0 && res.z == 1 && res.y >= 6 && res.y <= GM_INLINE && len >= 2);
@@ -732,243 +685,231 @@ struct GfLds {  // one read's staging
   int best[GF_CAND + AMG_MAX_K];
 };
 
-__device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi, int lane, GfLds& S) {
-  const CorrArgs& a = A.a;
-  const GView& g = A.g;
-  const int wv = 0;
-  int (*s_node)[GF_MAXW] = &S.node;
-  signed char (*s_dir)[GF_MAXW] = &S.dir;
-  int (*s_tok)[GF_MAXW + AMG_MAX_K] = &S.tok;
-  int (*s_gap)[GF_MAXGAP * 3] = &S.gap;
-  int (*s_pool)[GF_POOL] = &S.pool;
-  int* s_used = &S.used;
-  int (*s_cnode)[GF_CAND] = &S.cnode;
-  signed char (*s_cdir)[GF_CAND] = &S.cdir;
-  int (*s_gene)[GF_CAND + AMG_MAX_K] = &S.gene;
-  int (*s_best)[GF_CAND + AMG_MAX_K] = &S.best;
-  const GapRec rec = A.rec[gi];
-  const long long r = rec.r, t0 = rec.t0, dst = rec.dst;
-  const int L0 = rec.L0;
-  const int nwin = L0 - g.k + 1;
-  const int start = rec.start, end = rec.end;
-  if (nwin > GF_MAXW) {
-    if (lane == 0) A.need_slow[gi] = GS_WINDOWS;
-    return;
-  }
-  int* W = s_node[wv];
-  signed char* Dr = s_dir[wv];
-  int* TK = s_tok[wv];
-  int* GAP = s_gap[wv];
-  int* POOL = s_pool[wv];
+// ---- the steps of gapped_fast_read, each done by the whole wave on the read's staging S
+// the read's windows (nodes, directions) and genes
+__device__ __forceinline__ void gf_stage(const CorrArgs& a, const GapRec& rec, int nwin, int lane, GfLds& S) {
   for (int i = lane; i < nwin; i += 64) {
-    W[i] = a.tok_node[t0 + i];
-    Dr[i] = a.tok_dir[t0 + i];
+    S.node[i] = a.tok_node[rec.t0 + i];
+    S.dir[i] = a.tok_dir[rec.t0 + i];
   }
-  for (int i = lane; i < L0; i += 64) TK[i] = a.tokens[t0 + i];
-  // the read's question slots in the path memo ([0] < 0: none; entries past its runs are not initialised)
-  const int myslot = (A.gq && lane < GF_MAXGAP) ? A.gq[gi * GF_MAXGAP + lane] : -1;
-  if (lane == 0) s_used[wv] = 0;
+  for (int i = lane; i < rec.L0; i += 64) S.tok[i] = a.tokens[rec.t0 + i];
+  if (lane == 0) S.used = 0;
   wave_sync();
-  // ---- None runs in [start, end] (identify_path_terminals), in read order
+}
+
+// None runs in [start, end] (identify_path_terminals), in read order: S.gap of the first GF_MAXGAP; returns how many
+__device__ __forceinline__ int gf_list_runs(int start, int end, int lane, GfLds& S) {
   int n_gaps = 0;
   for (int c0 = start; c0 <= end; c0 += 64) {
     const int i = c0 + lane;
-    const bool is_end = i <= end && W[i] < 0 && W[i + 1] >= 0;  // i < end whenever W[i] < 0
+    const bool is_end = i <= end && S.node[i] < 0 && S.node[i + 1] >= 0;  // i < end whenever node[i] < 0
     const unsigned long long m = __ballot(is_end);
     if (is_end) {
       int q = n_gaps + __popcll(m & ((1ull << lane) - 1ull));
       if (q < GF_MAXGAP) {
         int ps = i - 1;
-        while (W[ps] < 0) --ps;
-        GAP[3 * q] = ps;
-        GAP[3 * q + 1] = i + 1;
-        GAP[3 * q + 2] = 0;
+        while (S.node[ps] < 0) --ps;
+        S.gap[3 * q] = ps;
+        S.gap[3 * q + 1] = i + 1;
+        S.gap[3 * q + 2] = 0;
       }
     }
     n_gaps += __popcll(m);
   }
-  if (n_gaps > GF_MAXGAP) {
-    if (lane == 0) A.need_slow[gi] = GS_RUNS;
-    return;
-  }
-  wave_sync();
-  // ---- the paths of every run, runs in read order: copied from the memo when the read's questions were entered
-  // there (k_gap_queries) — lane q looks run q up, then all copies are in flight together — otherwise one
-  // wave-cooperative DFS per run
-  const bool memo = __builtin_amdgcn_readfirstlane(myslot) >= 0;
-  bool bad = false;
-  int why = GS_RECORDS;
-  if (memo) {
-    int4 res = make_int4(0, 0, 0, 0);
-    if (lane < n_gaps) res = A.qres[myslot];
-    const int len = res.y > 0 ? res.y : 0;
-    int at = len;  // inclusive prefix over the runs (lanes < n_gaps <= 16)
+  return n_gaps;
+}
+
+// the runs' paths copied from the memo (k_gap_queries entered the read's questions): lane q looks run q up, then all
+// copies are in flight together.  Returns 0, or why the read is handed down.
+__device__ __forceinline__ int gf_paths_from_memo(const GapArgs& A, int myslot, int n_gaps, int lane, GfLds& S) {
+  int4 res = make_int4(0, 0, 0, 0);
+  if (lane < n_gaps) res = A.qres[myslot];
+  const int len = res.y > 0 ? res.y : 0;
+  int at = len;  // inclusive prefix over the runs (lanes < n_gaps <= 16)
 #pragma unroll
-    for (int d = 1; d < GF_MAXGAP; d <<= 1) {
-      const int o = __shfl_up(at, d, 64);
-      if (lane >= d) at += o;
-    }
-    const int total = __shfl(at, n_gaps - 1, 64);
-    at -= len;
-    bad = __any(res.y < 0) || total > GF_POOL;
-    if (__any(res.y < 0)) why = GS_MEMO_UNFIT;
-    if (!bad) {
-      for (int q = 0; q < n_gaps; ++q) {
-        const int src = __shfl(res.x, q, 64), ln = __shfl(len, q, 64), dst0 = __shfl(at, q, 64);
-        for (int i = lane; i < ln; i += 64) POOL[dst0 + i] = A.qpool[src + i];
-      }
-      wave_sync();
-      if (lane < n_gaps) {
-        for (int o = at; o < at + len; o += 2 + 2 * POOL[o + 1]) POOL[o] = lane;  // the records' run field
-        GAP[3 * lane + 2] = res.z;
-      }
-      if (lane == 0) s_used[wv] = total;
-      wave_sync();
-    }
-  } else {
-    for (int q = 0; q < n_gaps && !bad; ++q) {
-      const int ps = GAP[3 * q], pe = GAP[3 * q + 1];
-      const int np = dfs_paths_wave(g, W[ps], Dr[ps], W[pe], 2 * g.k, q, POOL, &s_used[wv], lane);
-      if (lane == 0) GAP[3 * q + 2] = np < 0 ? 0 : np;
-      bad = np < 0;
-    }
+  for (int d = 1; d < GF_MAXGAP; d <<= 1) {
+    const int o = __shfl_up(at, d, 64);
+    if (lane >= d) at += o;
   }
-  if (bad) {
-    if (lane == 0) A.need_slow[gi] = (unsigned char)why;
-    return;
+  const int total = __shfl(at, n_gaps - 1, 64);
+  at -= len;
+  if (__any(res.y < 0)) return GS_MEMO_UNFIT;
+  if (total > GF_POOL) return GS_RECORDS;
+  for (int q = 0; q < n_gaps; ++q) {
+    const int src = __shfl(res.x, q, 64), ln = __shfl(len, q, 64), dst0 = __shfl(at, q, 64);
+    for (int i = lane; i < ln; i += 64) S.pool[dst0 + i] = A.qpool[src + i];
   }
   wave_sync();
-  unsigned long long n_combo = 1;
-  bool dead_end = false;
+  if (lane < n_gaps) {
+    for (int o = at; o < at + len; o += 2 + 2 * S.pool[o + 1]) S.pool[o] = lane;  // the records' run field
+    S.gap[3 * lane + 2] = res.z;
+  }
+  if (lane == 0) S.used = total;
+  wave_sync();
+  return 0;
+}
+
+// without memo: one wave-cooperative search per run, runs in read order
+__device__ __forceinline__ int gf_paths_by_search(const GView& g, int n_gaps, int lane, GfLds& S) {
   for (int q = 0; q < n_gaps; ++q) {
-    int np = GAP[3 * q + 2];
+    const int ps = S.gap[3 * q], pe = S.gap[3 * q + 1];
+    const int np = dfs_paths_wave(g, S.node[ps], S.dir[ps], S.node[pe], 2 * g.k, q, S.pool, &S.used, lane);
+    if (lane == 0) S.gap[3 * q + 2] = np < 0 ? 0 : np;
+    if (np < 0) return GS_RECORDS;
+  }
+  return 0;
+}
+
+// candidates = the product of the runs' path counts (counted up to the first product beyond GF_MAXCOMBO)
+__device__ __forceinline__ unsigned long long gf_count_combos(const GfLds& S, int n_gaps, bool& dead_end) {
+  unsigned long long n_combo = 1;
+  dead_end = false;
+  for (int q = 0; q < n_gaps; ++q) {
+    const int np = S.gap[3 * q + 2];
     dead_end = dead_end || np == 0;
     n_combo *= (unsigned long long)np;
     if (n_combo > GF_MAXCOMBO) break;
   }
+  return n_combo;
+}
+
+__device__ __forceinline__ void gf_copy_windows(GfLds& S, int n, int i, int cnt, int lane) {
+  for (int j = lane; j < cnt; j += 64) {
+    S.cnode[n + j] = S.node[i + j];
+    S.cdir[n + j] = S.dir[i + j];
+  }
+}
+
+// candidate `combo` (mixed radix over the runs' paths, the LAST run varies fastest: itertools.product): the live
+// windows and the chosen path of every run into S.cnode / S.cdir.  Control flow is wave-uniform (one step per run, not
+// per window), the copies are lane-parallel.  Returns the candidate's nodes, -1 beyond GF_CAND.
+__device__ __forceinline__ int gf_build_candidate(GfLds& S, int start, int end, int n_gaps, int used,
+                                                  unsigned long long combo, int lane) {
+  int n = 0, i = start, prev_pe = -1;
+  for (int q = 0; q < n_gaps; ++q) {
+    const int ps = S.gap[3 * q], pe = S.gap[3 * q + 1], np = S.gap[3 * q + 2];
+    // windows [i, ps) are live (a None run is maximal): copied as they are
+    const int cnt = ps - i;
+    if (cnt > 0) {
+      if (n + cnt > GF_CAND) return -1;
+      gf_copy_windows(S, n, i, cnt, lane);
+      n += cnt;
+    }
+    unsigned long long div = 1;
+    for (int j = q + 1; j < n_gaps; ++j) div *= (unsigned long long)S.gap[3 * j + 2];
+    int pick = (int)((combo / div) % (unsigned long long)np);
+    int off = 0;
+    while (off < used) {  // records of run q appear in DFS order
+      if (S.pool[off] == q) {
+        if (pick == 0) break;
+        --pick;
+      }
+      off += 2 + 2 * S.pool[off + 1];
+    }
+    const int L = S.pool[off + 1];
+    if (prev_pe == ps && n > 0) --n;  // consecutive runs share their terminal node
+    if (n + L > GF_CAND) return -1;
+    for (int j = lane; j < L; j += 64) {
+      S.cnode[n + j] = S.pool[off + 2 + j];
+      S.cdir[n + j] = (signed char)S.pool[off + 2 + L + j];
+    }
+    n += L;
+    prev_pe = pe;
+    i = (q + 1 < n_gaps && S.gap[3 * (q + 1)] == pe) ? pe : pe + 1;
+  }
+  const int cnt = end - i + 1;
+  if (cnt > 0) {
+    if (n + cnt > GF_CAND) return -1;
+    gf_copy_windows(S, n, i, cnt, lane);
+    n += cnt;
+  }
+  return n;
+}
+
+// the candidate's ng = n + k - 1 genes (get_annotation_for_read) into S.gene and, when candidates are ranked against
+// each other, its coverage sum and len(set(genes) & set(original genes)); lane-parallel
+__device__ __forceinline__ void gf_spell_and_score(const GView& g, GfLds& S, int n, int L0, bool rank, int lane,
+                                                   int& shared, unsigned long long& csum) {
+  const int ng = n + g.k - 1;
+  shared = 0;
+  csum = 0;
+  for (int q = lane; q < ng; q += 64) {
+    const int idx = q < g.k - 1 ? 0 : q - (g.k - 1);
+    const int j = q < g.k - 1 ? q : g.k - 1;
+    S.gene[q] = oriented_tok(g, S.cnode[idx], S.cdir[idx], j);
+  }
+  if (rank) {
+    for (int q = lane; q < n; q += 64) csum += g.n_cov[S.cnode[q]];
+    for (int d = 32; d > 0; d >>= 1) csum += __shfl_xor(csum, d, 64);
+  }
+  wave_sync();
+  if (rank) {
+    for (int q = lane; q < ng; q += 64) {
+      const int tk = S.gene[q];
+      bool dup = false;
+      for (int w = 0; w < q && !dup; ++w) dup = (S.gene[w] == tk);
+      bool hit = false;
+      if (!dup)
+        for (int w = 0; w < L0 && !hit; ++w) hit = (S.tok[w] == tk);
+      shared += hit ? 1 : 0;
+    }
+    for (int d = 32; d > 0; d >>= 1) shared += __shfl_xor(shared, d, 64);
+  }
+}
+
+__device__ __forceinline__ void gf_hand_down(const GapArgs& A, long long gi, int lane, int why) {
+  if (lane == 0) A.need_slow[gi] = (unsigned char)why;
+}
+
+// One read, re-threaded by one wave.  The first limit exceeded hands the read to the general kernel (GS_*).
+__device__ __forceinline__ void gapped_fast_read(const GapArgs& A, long long gi, int lane, GfLds& S) {
+  const CorrArgs& a = A.a;
+  const GView& g = A.g;
+  const GapRec rec = A.rec[gi];
+  const int nwin = rec.L0 - g.k + 1;
+  if (nwin > GF_MAXW) return gf_hand_down(A, gi, lane, GS_WINDOWS);
+  // the read's question slots in the path memo ([0] < 0: none; entries past its runs are not initialised)
+  const int myslot = (A.gq && lane < GF_MAXGAP) ? A.gq[gi * GF_MAXGAP + lane] : -1;
+  gf_stage(a, rec, nwin, lane, S);
+  const int n_gaps = gf_list_runs(rec.start, rec.end, lane, S);
+  if (n_gaps > GF_MAXGAP) return gf_hand_down(A, gi, lane, GS_RUNS);
+  wave_sync();
+  const int unfit = __builtin_amdgcn_readfirstlane(myslot) >= 0 ? gf_paths_from_memo(A, myslot, n_gaps, lane, S)
+                                                                : gf_paths_by_search(g, n_gaps, lane, S);
+  if (unfit) return gf_hand_down(A, gi, lane, unfit);
+  wave_sync();
+  bool dead_end;
+  const unsigned long long n_combo = gf_count_combos(S, n_gaps, dead_end);
   if (dead_end) {
-    // possible_paths == []: the original genes (and positions) are kept (:1292-1293);
-    // the pack step copies them
+    // possible_paths == []: the original genes (and positions) are kept (:1292-1293); the pack step copies them
     if (lane == 0) {
-      a.new_len[r] = (unsigned int)L0;
-      A.final_cls[r] = RC_KEEP_ORIG;
+      a.new_len[rec.r] = (unsigned int)rec.L0;
+      A.final_cls[rec.r] = RC_KEEP_ORIG;
     }
     return;
   }
-  if (n_combo > GF_MAXCOMBO) {
-    if (lane == 0) A.need_slow[gi] = GS_COMBOS;
-    return;
-  }
-  int* CN = s_cnode[wv];
-  signed char* CD = s_cdir[wv];
-  int* GN = s_gene[wv];
-  int* BEST = s_best[wv];
-  const int used = s_used[wv];
+  if (n_combo > GF_MAXCOMBO) return gf_hand_down(A, gi, lane, GS_COMBOS);
+  const int used = S.used;
   int best_shared = 0, best_ng = -1;
   unsigned long long best_sum = 0, best_len = 1;
   for (unsigned long long combo = 0; combo < n_combo; ++combo) {
-    // ---- candidate node list: live windows + the chosen path of every run.  Control flow is
-    // wave-uniform (one step per run, not per window), the copies are lane-parallel.
-    int n = 0;
-    {
-      int i = start, prev_pe = -1;
-      bool over = false;
-      for (int q = 0; q < n_gaps && !over; ++q) {
-        const int ps = GAP[3 * q], pe = GAP[3 * q + 1], np = GAP[3 * q + 2];
-        // windows [i, ps) are live (a None run is maximal): copied as they are
-        const int cnt = ps - i;
-        if (cnt > 0) {
-          if (n + cnt > GF_CAND) { over = true; break; }
-          for (int j = lane; j < cnt; j += 64) {
-            CN[n + j] = W[i + j];
-            CD[n + j] = Dr[i + j];
-          }
-          n += cnt;
-        }
-        unsigned long long div = 1;
-        for (int j = q + 1; j < n_gaps; ++j) div *= (unsigned long long)GAP[3 * j + 2];
-        int pick = (int)((combo / div) % (unsigned long long)np);
-        int off = 0;
-        while (off < used) {  // records of run q appear in DFS order
-          if (POOL[off] == q) {
-            if (pick == 0) break;
-            --pick;
-          }
-          off += 2 + 2 * POOL[off + 1];
-        }
-        const int L = POOL[off + 1];
-        if (prev_pe == ps && n > 0) --n;  // consecutive runs share their terminal node
-        if (n + L > GF_CAND) { over = true; break; }
-        for (int j = lane; j < L; j += 64) {
-          CN[n + j] = POOL[off + 2 + j];
-          CD[n + j] = (signed char)POOL[off + 2 + L + j];
-        }
-        n += L;
-        prev_pe = pe;
-        i = (q + 1 < n_gaps && GAP[3 * (q + 1)] == pe) ? pe : pe + 1;
-      }
-      if (!over) {
-        const int cnt = end - i + 1;
-        if (cnt > 0) {
-          if (n + cnt > GF_CAND) {
-            over = true;
-          } else {
-            for (int j = lane; j < cnt; j += 64) {
-              CN[n + j] = W[i + j];
-              CD[n + j] = Dr[i + j];
-            }
-            n += cnt;
-          }
-        }
-      }
-      if (over) n = -1;
-    }
+    const int n = gf_build_candidate(S, rec.start, rec.end, n_gaps, used, combo, lane);
     wave_sync();
-    if (n < 0) {
-      if (lane == 0) A.need_slow[gi] = GS_CAND;
-      return;
-    }
-    const int ng = n + g.k - 1;
-    // ---- genes (get_annotation_for_read) and coverage sum, lane-parallel
-    unsigned long long csum = 0;
-    for (int q = lane; q < ng; q += 64) {
-      const int idx = q < g.k - 1 ? 0 : q - (g.k - 1);
-      const int j = q < g.k - 1 ? q : g.k - 1;
-      GN[q] = oriented_tok(g, CN[idx], CD[idx], j);
-    }
-    if (n_combo > 1) {  // the mean coverage only ranks candidates against each other
-      for (int q = lane; q < n; q += 64) csum += g.n_cov[CN[q]];
-      for (int d = 32; d > 0; d >>= 1) csum += __shfl_xor(csum, d, 64);
-    }
-    wave_sync();
-    bool better = true;
-    if (n_combo > 1) {
-      // len(set(genes) & set(original genes))
-      int shared = 0;
-      for (int q = lane; q < ng; q += 64) {
-        const int tk = GN[q];
-        bool dup = false;
-        for (int w = 0; w < q && !dup; ++w) dup = (GN[w] == tk);
-        bool hit = false;
-        if (!dup)
-          for (int w = 0; w < L0 && !hit; ++w) hit = (TK[w] == tk);
-        shared += hit ? 1 : 0;
-      }
-      for (int d = 32; d > 0; d >>= 1) shared += __shfl_xor(shared, d, 64);
-      better = shared > best_shared ||
-               (shared == best_shared && csum * best_len > best_sum * (unsigned long long)n);
-      if (better) best_shared = shared;
-    }
-    if (better) {
+    if (n < 0) return gf_hand_down(A, gi, lane, GS_CAND);
+    int shared;
+    unsigned long long csum;
+    gf_spell_and_score(g, S, n, rec.L0, n_combo > 1, lane, shared, csum);  // (a lone candidate is not ranked)
+    if (n_combo == 1 || cand_better(shared, csum, n, best_shared, best_sum, best_len)) {
+      best_shared = shared;
       best_sum = csum;
       best_len = (unsigned long long)n;
-      best_ng = ng;
-      for (int q = lane; q < ng; q += 64) BEST[q] = GN[q];
+      best_ng = n + g.k - 1;
+      for (int q = lane; q < best_ng; q += 64) S.best[q] = S.gene[q];
     }
     wave_sync();
   }
-  for (int q = lane; q < best_ng; q += 64) a.tmp_tok[dst + q] = BEST[q];
-  if (lane == 0) a.new_len[r] = (unsigned int)best_ng;
+  for (int q = lane; q < best_ng; q += 64) a.tmp_tok[rec.dst + q] = S.best[q];
+  if (lane == 0) a.new_len[rec.r] = (unsigned int)best_ng;
 }
 
 // left == nullptr: every re-threaded read, one per workgroup; else the reads k_corr_gapped_lean flagged: a workgroup

@@ -54,6 +54,49 @@ def test_paths_between_junctions_one_search_per_start(case):
     assert n_paths > 0 or not starts
 
 
+def _paths_per_start(g, distance):
+    """{start junction: the paths the reference's double loop keeps for it, stop by stop, in search order}"""
+    want = {}
+    for junctions in g.identify_potential_bubble_starts().values():
+        for start in junctions:
+            for stop in junctions:
+                if start[0] == stop[0]:
+                    continue
+                found = g.new_find_paths_between_nodes(start[0], stop[0], distance, start[1])
+                valid = [p for p in found if p[0] == start
+                         and (p[-1][0], g.get_direction_between_two_nodes(p[-2][0], p[-1][0])) == stop]
+                if len(valid) > 1:
+                    want.setdefault(start, []).extend(valid)
+    return want
+
+
+def test_junction_search_prunes_at_every_distance():
+    """the search's bound is the junction visitor's answer to the shared search loop, and bubble popping only ever asks
+    for 4k: the paths per (start, stop) pair at distances 2, 3 and 4k against new_find_paths_between_nodes"""
+    g, _ = _graph(*CASES[0])
+    assert g is not None
+    v = g._v()
+    k4 = g.get_kmerSize() * 4
+    n_paths, exact = {}, False
+    for d in (2, 3, k4):
+        found = g._engine.junction_paths(d)
+        assert found["flags"] == 0
+        v.ensure_hashes(np.unique(np.concatenate([found["path_node"], found["junction_node"]])).tolist())
+        junction = [(v.node_hash[n], s) for n, s in zip(found["junction_node"].tolist(), found["junction_dir"].tolist())]
+        off, ids, dirs = found["path_off"].tolist(), found["path_node"].tolist(), found["path_dir"].tolist()
+        got = {}
+        for p, j in enumerate(found["path_start"].tolist()):
+            got.setdefault(junction[j], []).append([(v.node_hash[i], s) for i, s in zip(ids[off[p]:off[p + 1]],
+                                                                                         dirs[off[p]:off[p + 1]])])
+        want = _paths_per_start(g, d)
+        assert got == want
+        n_paths[d] = sum(len(x) for x in want.values())
+        exact = exact or any(len(p) == d for x in want.values() for p in x)
+    # not vacuous: a path that uses the whole distance, and a distance that cuts paths off
+    assert exact
+    assert min(n_paths[2], n_paths[3]) < n_paths[k4]
+
+
 @pytest.mark.parametrize("case", CASES[:3])
 def test_sketch_sizes_and_overlaps(case):
     g, fq = _graph(*case)
