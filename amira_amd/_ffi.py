@@ -134,6 +134,7 @@ def _load():
         "amg_set_timing": (C.c_int, [P, C.c_int]),
         "amg_scan_probe": (C.c_int, [P, C.c_int, P, I64, P, P]),
         "amg_count_probe": (C.c_int, [P, C.c_int, C.c_int, P, I64, I64, P, I64, C.c_int, C.c_int, P, P]),
+        "amg_nw_probe": (C.c_int, [P, I64, P, P, P, P, P, P, P, P, C.c_int, P, P, P, P]),
         "amg_correct_routes": (C.c_int, [P, P, I32]),
     }
     for name, (res, args) in sig.items():

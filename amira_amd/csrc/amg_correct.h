@@ -171,7 +171,12 @@ struct NwArgs {
   unsigned char* big_buf;
   int allow_fast;            // 0: every read takes the general kernel (debugging / A-B switch)
   int shortcuts;             // 0: k_corr_nw_fast fills a matrix for every read (AMG_NW_NO_SHORTCUT=1: test switch)
+  unsigned char* route;      // per gapped read, or nullptr (amg_correct_reads): what settled it in k_corr_nw_fast, a
+                             // NW_ROUTE_* code (amg_nw_probe)
 };
+// how a carry-over was made (amg_nw_probe's route byte; include/amg.h).  k_corr_nw_fast writes the first three, the
+// others follow from the record and the sizes of k_nw_sizes
+enum { NW_ROUTE_NONE = 0, NW_ROUTE_EQUAL = 1, NW_ROUTE_CERT = 2, NW_ROUTE_FILL = 3, NW_ROUTE_LDS = 4, NW_ROUTE_GLOBAL = 5 };
 
 // ---- compaction into the corrected CSR: a read is kept when len(list_of_genes) > 0 (:1130)
 struct PackArgs {
@@ -266,7 +271,8 @@ int corr_nw_sizes(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, cons
                   FetchList& shape);
 // stage correct_positions: room for what this call produces (may MOVE the pools: fill_pos_args again), then the kernels
 int corr_grow_pos_pools(amg_ctx* c, const CorrCounts& n);
-int corr_positions(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n);
+int corr_positions(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n,
+                   unsigned char* route = nullptr);  // route: NwArgs::route (amg_nw_probe only)
 
 // ---- route report (amg_correct_routes.hip), only with CorrSwitches::routes: small tally kernels behind the steps
 int routes_begin(amg_ctx* c);

@@ -250,6 +250,27 @@ class Engine:
         check(_ffi.lib.amg_correct_routes(self._h, _ffi.ptr(out), len(out)))
         return dict(zip(self.ROUTES, out.tolist()))
 
+    NW_ROUTES = ("none", "equal_length", "certificate", "fill", "general_lds", "general_global")
+
+    def nw_probe(self, x, y, pos, read_len=None, keep_orig=None, flags=0):
+        """one position carry-over per pair (include/amg.h, amg_nw_probe): a test hook.  x, y: (tokens, offsets) of the
+        corrected and the original lists; pos: (start, end) per gene of y.  Returns the positions of the pairs that
+        are not keep_orig as (start, end), one route code per pair (NW_ROUTES) and the state words."""
+        (xt, xo), (yt, yo) = ((np.ascontiguousarray(t, np.int32), np.ascontiguousarray(o, np.int64)) for t, o in (x, y))
+        ps, pe = (np.ascontiguousarray(p, np.int64) for p in pos)
+        n = len(xo) - 1
+        assert len(yo) == n + 1 and len(ps) == len(pe) == len(yt)
+        rl = None if read_len is None else np.ascontiguousarray(read_len, np.int64)
+        keep = None if keep_orig is None else np.ascontiguousarray(keep_orig, np.uint8)
+        lens = np.diff(xo)
+        total = int(lens.sum() if keep is None else lens[keep == 0].sum())
+        gs, ge = np.zeros(max(total, 1), np.int64), np.zeros(max(total, 1), np.int64)
+        route, state = np.zeros(max(n, 1), np.uint8), np.zeros(8, np.int64)
+        check(_ffi.lib.amg_nw_probe(self._h, n, _ffi.ptr(xt) if xt.size else None, _ffi.ptr(xo), _ffi.ptr(yt),
+                                    _ffi.ptr(yo), _ffi.ptr(ps), _ffi.ptr(pe), _ffi.ptr(rl), _ffi.ptr(keep), int(flags),
+                                    _ffi.ptr(gs), _ffi.ptr(ge), _ffi.ptr(route), _ffi.ptr(state)))
+        return gs[:total], ge[:total], route[:n], state
+
     def corrected(self, n_reads, n_tokens, with_positions, buf=None, pos32=False):
         """the corrected set on the host.  pos32: the positions as int32 arrays (gathered on the device, half the bytes
         over PCIe) when every one of them fits — int64 otherwise, as without the flag"""

@@ -463,6 +463,32 @@ int amg_scan_probe(amg_ctx* ctx, int kind, const void* in, int64_t n, int64_t* o
 int amg_count_probe(amg_ctx* ctx, int kind, int form, int32_t* ids, int64_t n, int64_t n_ids, const int32_t* tab_ids,
                     int64_t n_slots, int misalign, int flags, uint32_t* counts, int64_t* state);
 
+/* ---- tests: one position carry-over per pair of gene lists on host arrays ----------------------------
+ * What the correct_positions stage of amg_correct_reads (amg_correct_nw.hip) makes of n_pairs pairs: pair p is the
+ * corrected list x_tok[x_off[p] .. x_off[p + 1]) against the original list y_tok[y_off[p] .. y_off[p + 1]), whose genes
+ * have the positions y_start / y_end (one entry per gene of y).  read_len: per pair, or NULL (no read lengths were
+ * set).  keep_orig: per pair non-zero = the read kept its original genes (no carry-over), or NULL.  The stage's own
+ * host steps and kernels run on these arrays: sizes and records, the scan pair, the shape fetch, the pools' growth,
+ * the placement, k_corr_nw_fast and k_corr_nw.
+ * flags: 1 = no fast kernel (as AMG_NO_FAST_NW), 2 = no shortcuts (as AMG_NW_NO_SHORTCUT), 4 = the original positions
+ * lie in the pool of PRODUCED positions (as those of a read re-threaded before), in an allocation made for them alone,
+ * so that what this call produces makes the pool move once it exceeds the allocator's slack (an eighth and 256 bytes).
+ * out_start / out_end: the positions of the pairs that are not keep_orig, N_p each, in pair order.
+ * route[p]: 0 no carry-over (keep_orig), 1 equal-length shortcut, 2 offset-diagonal certificate, 3 k_corr_nw_fast
+ * filled its matrix, 4 k_corr_nw in LDS, 5 k_corr_nw in global scratch.
+ * state[8]: [0] bytes of global scratch, [1] positions produced, [2] pairs for k_corr_nw (the three totals of the
+ * shape fetch), [3] 1 = the guard words in front of and behind the produced positions and behind the staged genes are
+ * intact (and, with flag 4, the original positions in the pool), [4] 1 = the pool of produced positions moved, 0 = its
+ * slack held what was produced.
+ * Refused with AMG_E_ARG before anything runs: a negative gene, an empty y, an empty x on a pair that is not
+ * keep_orig, lists beyond 2^24 genes or 1 GiB of matrix scratch, n_pairs outside [1, 2^20].  The context's reads,
+ * positions and graph are as they were afterwards; the stage's scratch (records, matrix scratch, status word), which
+ * every amg_correct_reads call fills anew, is overwritten. */
+int amg_nw_probe(amg_ctx* ctx, int64_t n_pairs, const int32_t* x_tok, const int64_t* x_off, const int32_t* y_tok,
+                 const int64_t* y_off, const int64_t* y_start, const int64_t* y_end, const int64_t* read_len,
+                 const uint8_t* keep_orig, int flags, int64_t* out_start, int64_t* out_end, uint8_t* route,
+                 int64_t* state);
+
 /* ---- tests: which read took which route through the last amg_correct_reads call ----------------------
  * With AMG_CORR_ROUTES=1 in the environment of an amg_correct_reads call, small tally kernels run behind its steps
  * (without it the call launches and reads back what it always did).  amg_correct_routes copies the tallies of the

@@ -15,9 +15,11 @@ Oracle time per case on one CPU core (build + filter + correct + rebuild), measu
 every case below 1 s except the 1 100-gene read (about 3 s), the 2 000-gene read (about 10 s) and the whole sweeps at
 k = 15 / 16 and over tandem arrays (2 - 6 s each).
 
-Not covered: N = 128 corrected genes against M <= 64 original ones (the far corner of nw_fast_ok): a None run adds at
-most about k genes, so real reads cannot get there.  A single path record only exceeds GM_INLINE at k = 16 (a path of
-2k = 32 nodes is 2 + 64 ints; at k = 15 the longest is 62 ints), so the k = 15 read of that case stays inline."""
+Not covered HERE: N = 128 corrected genes against M <= 64 original ones (the far corner of nw_fast_ok): a None run
+adds at most about k genes, so real reads cannot get there.  tests/test_gpu_carry_over.py hands the carry-over kernels
+such pairs directly (amg_nw_probe), with every other shape at their limits.  A single path record only exceeds
+GM_INLINE at k = 16 (a path of 2k = 32 nodes is 2 + 64 ints; at k = 15 the longest is 62 ints), so the k = 15 read of
+that case stays inline."""
 import numpy as np
 import pytest
 
