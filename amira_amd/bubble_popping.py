@@ -8,8 +8,12 @@ What grows with the data runs on the device, on the device's own node ids (amira
     where the reference searches once per (start, stop) pair (`Engine.junction_paths`);
   * the sketches: the reads' bases are uploaded once per cleaning run (`Sequences`), a node's sketch is hashed straight
     from them under every window that sits on the node, the paths' sketches are united and compared on the device
-    (`Engine.path_sketch_overlaps`) — the host sees sketch sizes and overlaps, never a hash.
-What decides with those numbers — which path of a bubble is the better one, which reads are rewritten and how — is
+    (`Engine.path_sketch_overlaps`) — the host sees sketch sizes and overlaps, never a hash;
+  * the rewriting of the reads: the alignment of every correction operation's two gene lists and, per assigned read,
+    the orientation vote, the shared run, the second alignment and the splice, all operations and reads of one
+    correct_bubble_paths in ONE call (`Engine.pop_rewrite`, amira_amd/csrc/amg_pop.hip; AMG_POP_REWRITE=0: the loop
+    below instead) — the host spells the new genes and repairs the positions.
+What decides with those numbers — which path of a bubble is the better one, which reads go with which operation — is
 host-side orchestration over a handful of paths, as in the reference.  A graph edited on the host (add_node, ...) and
 the cases the device path leaves alone (a gene-mer size beyond 16: 4 k > 64 levels of search; two nodes joined by
 several edges at the end of a path, where the reference fails; AMG_BUBBLES_BY_OBJECTS=1, the A/B and test switch) go
@@ -414,6 +418,10 @@ class BubblePopping:
                     by_coverage, path_coverages, reads_to_correct, correction_operations, path_minimizers,
                     seen_nodes, threshold)
         self.get_path_reads_to_correct(reads_to_correct, seen_nodes)
+        if (correction_operations and reads_to_correct and not self._host_edits
+                and not os.environ.get("AMG_BUBBLES_BY_OBJECTS") and os.environ.get("AMG_POP_REWRITE", "1") != "0"
+                and self._rewrite_reads_on_device(correction_operations, reads_to_correct, genesOfInterest, fastq_data)):
+            return path_coverages
         k = self.get_kmerSize()
         plans = {}   # operation -> (alignment, mirrored alignment, gene-mer counter, mirrored counter)
         spelled = {}   # (a better path is the better path of several worse ones)
@@ -454,6 +462,67 @@ class BubblePopping:
         return path_coverages
 
     # ------------------------------------------------------------------ the device's share
+    def _rewrite_reads_on_device(self, correction_operations, reads_to_correct, genesOfInterest, fastq_data):
+        """what correct_bubble_paths does with its operations and their reads, in ONE call (`Engine.pop_rewrite`,
+        amg_pop_rewrite): the alignments, the veto, the orientation vote, the shared run, the second alignment and the
+        splice happen on the device; new genes are spelled and positions repaired here.  False, with nothing changed,
+        when the call does not take the input — a size beyond its documented limits (`Engine.pop_rewrite_declines`: a
+        path of more than 128 genes), a gene string the vocabulary does not hold as it stands —: the loop over the
+        reads then runs as before, and `pop_rewrite_stats["declined"]` counts it.  The sizes are checked HERE, so any
+        error of the call itself is a bug and raises."""
+        vocab = self._vocab
+        token_of = vocab._tok
+        operations = list(correction_operations)
+        index_of = {operation: i for i, operation in enumerate(operations)}
+        spelled = {}   # (a better path is the better path of several worse ones)
+
+        def tokens_of(path):
+            got = spelled.get(path)
+            if got is None:
+                got = spelled[path] = [token_of.get(g) for g in self.get_genes_in_unitig(list(path))]
+            return got
+
+        better = [tokens_of(operation[1]) for operation in operations]
+        worse = [tokens_of(operation[0]) for operation in operations]
+        reads = self.get_reads()
+        read_ids = list(reads_to_correct)
+        old_genes = [reads[r] for r in read_ids]
+        rows = [[token_of.get(g) for g in genes] for genes in old_genes]
+        if (any(None in row for rows_ in (better, worse, rows) for row in rows_)
+                or self._engine.pop_rewrite_declines(self.get_kmerSize(), better, worse, rows)):
+            self._engine.pop_rewrite_stats["declined"] += 1
+            return False
+        interest = None
+        if genesOfInterest:
+            interest = np.zeros(vocab.two_v, np.uint8)
+            V = max(vocab.V, 1)
+            for name in genesOfInterest:
+                rank = vocab.rank.get(name)
+                if rank is not None:
+                    interest[V + rank] = interest[V - 1 - rank] = 1
+
+        def csr(lists):
+            off = np.zeros(len(lists) + 1, np.int64)
+            np.cumsum([len(x) for x in lists], out=off[1:])
+            return np.fromiter((t for x in lists for t in x), np.int32, int(off[-1])), off
+
+        got = self._engine.pop_rewrite(self.get_kmerSize(), vocab.two_v, *csr(better), *csr(worse), interest,
+                                       *csr(rows), [index_of[reads_to_correct[r]] for r in read_ids])
+        status = got["status"].tolist()
+        off, new_tokens, source = got["out_off"].tolist(), got["out_tok"], got["out_src"].tolist()
+        all_positions = self.get_gene_positions()
+        for i, read_id in enumerate(read_ids):
+            if status[i] != 2:
+                continue
+            a, b = off[i], off[i + 1]
+            reads[read_id] = vocab.decode(new_tokens[a:b])
+            positions = all_positions[read_id]
+            joined = [positions[s] if s >= 0 else (None, None) for s in source[a:b]]
+            all_positions[read_id] = self.replace_invalid_gene_positions(joined, fastq_data, read_id)
+            n_genes, n_pos = len(reads[read_id]), len(all_positions[read_id])
+            assert n_genes == n_pos, f"{n_genes}/{n_pos}"
+        return True
+
     def _junction_paths_on_device(self):
         """{component: [path, ...]} with every path get_all_paths_between_junctions_in_component would add to its set,
         in the order it would add them, as lists of (node hash, direction) — and the components in order; None when the

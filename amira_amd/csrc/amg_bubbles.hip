@@ -752,7 +752,10 @@ extern "C" int amg_path_sketch_overlaps(amg_ctx* c, const amg_seqs* seqs, const 
 // needleman_wunsch (construct_graph.py:1433-1480) on interned genes: match 1, mismatch 0, gap -1, borders -index, the
 // best of (score, pointer) with the pointers ordered DIAG < LEFT < UP — a tie goes UP, then LEFT.  ops, in alignment
 // order: 0 = (x, y), 1 = (x, *), 2 = (*, y); at most n + m of them.  The two paths of a bubble are a few dozen genes:
-// this is the host's share of compare_paths (:1566), called once per correction operation.
+// this is the host's share of compare_paths (:1566) where bubble popping rewrites its reads in the loop on the host
+// (AMG_POP_REWRITE=0, AMG_BUBBLES_BY_OBJECTS=1, a graph edited on the host, a path beyond amg_pop_rewrite's 128 genes):
+// once per correction operation, and once per read whose stretch differs.  By default amg_pop_rewrite (amg_pop.hip)
+// computes the same recurrence and traceback on the device.
 extern "C" int amg_nw_align(const int32_t* x, int32_t n, const int32_t* y, int32_t m, int8_t* ops, int32_t* n_ops) {
   if (n < 0 || m < 0 || !n_ops || ((n || m) && !ops) || (n && !x) || (m && !y)) return amg_fail(AMG_E_ARG, "bad argument");
   const int W = m + 1;

@@ -153,6 +153,7 @@ static inline int overflowed(Overflow* which, Overflow cause) { return *which = 
 
 struct DistState;  // amg_dist.h: communicator, buffers and progress of the ctx's merged builds
 struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until the caller has fetched it
+struct PopState;     // amg_pop.hip: the buffers of amg_pop_rewrite
 
 struct amg_ctx {
   int device = 0;
@@ -275,6 +276,7 @@ struct amg_ctx {
   uint32_t dist_min_node = 1, dist_min_edge = 1;  // fused filter of the next merged build
   DistState* dist = nullptr;
   BubbleState* bub = nullptr;  // amg_bubbles.hip
+  PopState* pop = nullptr;     // amg_pop.hip
 
   // ---- K6 result cache (two-call protocol of amg_match_patterns)
   bool match_valid = false;
@@ -413,6 +415,7 @@ struct GView {
 int ensure_live_adj(amg_ctx* c);  // the live lists below exist and are up to date
 GView make_view(amg_ctx* c);
 void bubbles_release(amg_ctx* c);
+void pop_release(amg_ctx* c);  // amg_pop.hip
 
 void dist_release(amg_ctx* c);  // amg_dist.hip
 // amg_derive.hip

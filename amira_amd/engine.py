@@ -19,6 +19,9 @@ class Engine:
         # there are any, the engine stays out of the pool
         self._leases = weakref.WeakSet()
         self._pool_when_free = False
+        # of pop_rewrite, over the engine's life; declined: correct_bubble_paths calls that went to the host loop
+        # because their input is beyond the call's limits
+        self.pop_rewrite_stats = {"calls": 0, "reads": 0, "rewritten": 0, "declined": 0}
 
     def close(self):
         if self._h:
@@ -412,6 +415,52 @@ class Engine:
         check(_ffi.lib.amg_path_sketch_overlaps(self._h, seqs._h, ptr(rts), int(ksize), int(scaled), n_paths, ptr(path_off),
                                                 ptr(path_node), n_pairs, ptr(pair_a), ptr(pair_b), ptr(size), ptr(common)))
         return size[:n_paths], common[:n_pairs]
+
+    # amg_pop_rewrite's limits (include/amg.h): genes of a better / worse list, operations or reads, genes of a read
+    POP_MAX_LIST, POP_MAX_ITEMS, POP_MAX_READ = 128, 1 << 20, 1 << 24
+
+    @classmethod
+    def pop_rewrite_declines(cls, k, better, worse, reads):
+        """True where pop_rewrite would refuse these lists of tokens for their SIZES alone (the caller then keeps its
+        loop on the host): any other refusal of the call is an error of the caller's"""
+        return (not 1 <= k <= 16 or not 1 <= len(better) <= cls.POP_MAX_ITEMS or not 1 <= len(reads) <= cls.POP_MAX_ITEMS
+                or any(not k <= len(x) <= cls.POP_MAX_LIST for lists in (better, worse) for x in lists)
+                or any(len(x) > cls.POP_MAX_READ for x in reads))
+
+    def pop_rewrite(self, k, two_v, better_tok, better_off, worse_tok, worse_off, interest, read_tok, read_off, read_op):
+        """the reads of one correct_bubble_paths call rewritten along their operations' alignments (amg_pop_rewrite):
+        operations and reads as CSR lists of tokens, interest a uint8 flag per token or None.  Returns a dict of
+        arrays: op_veto [operations], status / first_shared / last_shared [reads], out_off [reads + 1] and out_tok /
+        out_src packed behind it (entries for reads of status 2 only)."""
+        better_tok, worse_tok = np.ascontiguousarray(better_tok, np.int32), np.ascontiguousarray(worse_tok, np.int32)
+        better_off, worse_off = np.ascontiguousarray(better_off, np.int64), np.ascontiguousarray(worse_off, np.int64)
+        read_tok, read_off = np.ascontiguousarray(read_tok, np.int32), np.ascontiguousarray(read_off, np.int64)
+        read_op = np.ascontiguousarray(read_op, np.int32)
+        flags = None if interest is None else np.ascontiguousarray(interest, np.uint8)
+        assert flags is None or len(flags) == two_v
+        n_ops, n_reads = len(better_off) - 1, len(read_off) - 1
+        assert len(worse_off) == n_ops + 1 and len(read_op) == n_reads
+        cap = int(read_off[-1])
+        if n_ops > 0 and n_reads > 0 and 0 <= int(read_op.min()) and int(read_op.max()) < n_ops:
+            cap += int(np.diff(better_off)[read_op].sum())
+        out = {"op_veto": np.zeros(max(n_ops, 1), np.uint8), "status": np.zeros(max(n_reads, 1), np.uint8),
+               "first_shared": np.zeros(max(n_reads, 1), np.int32), "last_shared": np.zeros(max(n_reads, 1), np.int32),
+               "out_off": np.zeros(max(n_reads, 0) + 1, np.int64), "out_tok": np.empty(max(cap, 1), np.int32),
+               "out_src": np.empty(max(cap, 1), np.int32)}
+        n_out = C.c_int64(0)
+        check(_ffi.lib.amg_pop_rewrite(self._h, int(k), int(two_v), n_ops, ptr(better_tok), ptr(better_off), ptr(worse_tok),
+                                       ptr(worse_off), ptr(flags), n_reads, ptr(read_tok), ptr(read_off), ptr(read_op), cap,
+                                       ptr(out["op_veto"]), ptr(out["status"]), ptr(out["first_shared"]),
+                                       ptr(out["last_shared"]), ptr(out["out_off"]), ptr(out["out_tok"]),
+                                       ptr(out["out_src"]), C.byref(n_out)))
+        for key, n in (("op_veto", n_ops), ("status", n_reads), ("first_shared", n_reads), ("last_shared", n_reads),
+                       ("out_tok", n_out.value), ("out_src", n_out.value)):
+            out[key] = out[key][:n]
+        stats = self.pop_rewrite_stats
+        stats["calls"] += 1
+        stats["reads"] += n_reads
+        stats["rewritten"] += int((out["status"] == 2).sum())
+        return out
 
     # ---- multi-GPU: read shards + key-owner table merge (include/amg.h; drivers in amira_amd/dist.py)
     @staticmethod

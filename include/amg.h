@@ -303,6 +303,32 @@ int amg_path_sketch_overlaps(amg_ctx* ctx, const amg_seqs* seqs, const int32_t* 
  * gap -1, ties UP > LEFT > DIAG as the reference's max over (score, pointer) gives them.  ops (room for n + m), in
  * alignment order: 0 = (x gene, y gene), 1 = (x gene, "*"), 2 = ("*", y gene). */
 int amg_nw_align(const int32_t* x, int32_t n, const int32_t* y, int32_t m, int8_t* ops, int32_t* n_ops);
+/* The reads of all correction operations of one correct_bubble_paths call rewritten on the device (:1833-1955 from the
+ * alignments on: compare_paths :1737-1745, the veto :1880-1884, reorient_alignment :1591-1612, longest_common_sublist
+ * :1992-2014, modify_alignment_subset :1731-1735, correct_genes_on_read :1616-1628, get_new_gene_position_core :1641-1654).
+ * All arrays are HOST memory; the ctx gives the device, the stream and scratch — its reads, positions and graph are not
+ * touched, and it need not hold a graph.  Tokens are those of amg_set_reads (strand flip = two_v - 1 - token).
+ * In:  n_ops operations as two CSR lists of tokens, better_* the genes of the higher-coverage path, worse_* those of the
+ *      lower-coverage one (offsets [n_ops + 1]); interest [two_v], non-zero for a token of a gene of interest, or NULL;
+ *      n_reads reads as CSR (read_tok, read_off [n_reads + 1]) with read_op[r] the operation read r is rewritten by.
+ * Out: op_veto [n_ops] — 1: the operation would put a gene of interest of the worse path against a gap or against a gene
+ *      that is none, and is dropped; status [n_reads] — 0: the read's operation is vetoed, 1: as many DISTINCT gene-mers
+ *      of the read occur along the worse path read forwards as backwards (0 : 0 included), the read is left alone,
+ *      2: rewritten; first_shared / last_shared [n_reads] — the stretch of the old read that was replaced (-1 unless
+ *      status 2); out_off [n_reads + 1], out_tok / out_src packed in read order, entries only for reads of status 2:
+ *      the new genes and, per gene, the index into the OLD read of the gene whose position it keeps, -1 for none;
+ *      *n_out = out_off[n_reads].  cap = room in out_tok / out_src, at least the sum over the reads of (genes of the
+ *      read + genes of its operation's better list); nothing is written at or beyond *n_out.
+ * AMG_E_ARG before anything runs (no output is touched): k outside [1, 16], a better or worse list of more than 128 or
+ * fewer than k genes, a token outside [0, two_v), read_op out of range, a read of more than 2^24 genes, n_ops or n_reads
+ * outside [1, 2^20], cap below the bound.  The limits say what is computed correctly, not what is cheap: a wave walks its
+ * whole read and the plans take 2.2 KB per operation (AMG_E_NOMEM where that does not fit); bubble popping hands over a
+ * few thousand operations and reads of some dozens of genes. */
+int amg_pop_rewrite(amg_ctx* ctx, int32_t k, int32_t two_v, int64_t n_ops, const int32_t* better_tok,
+                    const int64_t* better_off, const int32_t* worse_tok, const int64_t* worse_off, const uint8_t* interest,
+                    int64_t n_reads, const int32_t* read_tok, const int64_t* read_off, const int32_t* read_op, int64_t cap,
+                    uint8_t* op_veto, uint8_t* status, int32_t* first_shared, int32_t* last_shared, int64_t* out_off,
+                    int32_t* out_tok, int32_t* out_src, int64_t* n_out);
 
 /* ---- multi-GPU: read-sharded build with a key-owner table merge — the single-graph result of
  *      build_multiprocessed_graph + merge_graphs (graph_utils.py:94-124) at cores = 1.
