@@ -1,6 +1,11 @@
 """GPU parity of filter -> correct_reads -> rebuild -> clip -> correct_reads -> rebuild
 (the cleaning sweep of graph_utils.py:145-166) against the CPU oracle, at the array level
-of the C ABI."""
+of the C ABI.
+
+run_sweep is sweep_begin (reads to the engine, first build) followed by one sweep_iteration, and a sweep can be
+continued: sweep_iteration returns the oracle graph, read ids and offsets of its third graph, which is what another
+sweep_iteration starts from without a new set_reads (tests/test_gpu_derive.py runs a second cleaning iteration on the
+derived third graph that way)."""
 import numpy as np
 import pytest
 
@@ -21,7 +26,9 @@ def eng():
 DERIVED = []   # per run_sweep: was the third graph made from the second one's live part (amg_derive.hip)?
 
 
-def run_sweep(eng, reads, pos, fq, k, min_cov=3):
+def sweep_begin(eng, reads, pos, fq, k):
+    """reads and positions to the engine, first build on both sides, compared: (g1, vocab, read_ids, offs), what
+    sweep_iteration goes on from"""
     from amira_amd import tokenize
     from amira_oracle import GeneMerGraph
     vocab, toks, offs, read_ids = tokenize(reads)
@@ -34,14 +41,34 @@ def run_sweep(eng, reads, pos, fq, k, min_cov=3):
     eng.build(k)
     g1 = GeneMerGraph(reads, k, pos)
     compare_engine_to_oracle(eng, oracle_arrays(g1, vocab, read_ids, offs, k))
+    return g1, vocab, read_ids, offs
+
+
+def sweep_iteration(eng, g1, vocab, read_ids, offs, fq, k, min_cov=3, verdicts=None):
+    """one cleaning iteration from "engine already built, oracle graph given" (g1 is the oracle's graph of the reads
+    the engine holds, ids `read_ids`, offsets `offs`): filter, correct, rebuild, clip, correct, rebuild, compared with
+    the oracle after every step.  Returns (g3, ids3, offs3, n_removed): the same four things for the third graph, so
+    that another iteration can follow without set_reads.  verdicts: a list that receives, per rebuild, (what
+    derive_cases.predicted_derivable said of the oracle graph just before its correct_reads, counts()["derived"])"""
+    from amira_oracle import GeneMerGraph
+
+    def predicted(g):
+        if verdicts is None:
+            return None
+        from derive_cases import predicted_derivable
+        return predicted_derivable(g, False)     # (filter(n, 1) and the tip clip remove no edge on its own)
+
     eng.filter(min_cov, 1)
     g1.filter_graph(min_cov, 1)
     compare_engine_to_oracle(eng, oracle_arrays(g1, vocab, read_ids, offs, k), live_only=True)
+    said = predicted(g1)
     r2, p2 = g1.correct_reads(fq)
     ids2, out2 = check_corrected(eng, vocab, read_ids, r2, p2)
 
     eng.adopt_corrected()
     eng.build(k)
+    if verdicts is not None:
+        verdicts.append((said, eng.counts()["derived"]))
     g2 = GeneMerGraph(r2, k, p2)
     compare_engine_to_oracle(eng, oracle_arrays(g2, vocab, ids2, out2["read_offsets"], k))
     removed = eng.remove_short_linear_paths(k)
@@ -49,15 +76,24 @@ def run_sweep(eng, reads, pos, fq, k, min_cov=3):
     want_removed = sorted(order[h] for h in g2.remove_short_linear_paths(k))
     assert sorted(removed.tolist()) == want_removed
     compare_engine_to_oracle(eng, oracle_arrays(g2, vocab, ids2, out2["read_offsets"], k), live_only=True)
+    said = predicted(g2)
     r3, p3 = g2.correct_reads(fq)
     ids3, out3 = check_corrected(eng, vocab, ids2, r3, p3)
 
     eng.adopt_corrected()
     eng.build(k)
+    if verdicts is not None:
+        verdicts.append((said, eng.counts()["derived"]))
     g3 = GeneMerGraph(r3, k, p3)
     compare_engine_to_oracle(eng, oracle_arrays(g3, vocab, ids3, out3["read_offsets"], k))
+    return g3, ids3, out3["read_offsets"], len(want_removed)
+
+
+def run_sweep(eng, reads, pos, fq, k, min_cov=3):
+    g1, vocab, read_ids, offs = sweep_begin(eng, reads, pos, fq, k)
+    n_removed = sweep_iteration(eng, g1, vocab, read_ids, offs, fq, k, min_cov)[3]
     DERIVED.append(eng.counts().get("derived", 0))
-    return len(want_removed)
+    return n_removed
 
 
 @pytest.mark.parametrize("seed,N,L,V,k,err", [(7, 400, 30, 300, 5, 0.03), (11, 400, 24, 200, 3, 0.03),
