@@ -99,6 +99,12 @@ def _load():
         "amg_seqs_create": (C.c_int, [I32, P, P, I64, C.POINTER(P)]),
         "amg_seqs_destroy": (C.c_int, [P]),
         "amg_path_sketch_overlaps": (C.c_int, [P, P, P, I32, C.c_uint64, I64, P, P, I64, P, P, P, P]),
+        "amg_kcount_create": (C.c_int, [P, P, I32, I32, C.POINTER(P)]),
+        "amg_kcount_sizes": (C.c_int, [P, P]),
+        "amg_kcount_histo": (C.c_int, [P, P, I64, P]),
+        "amg_kcount_query": (C.c_int, [P, P, P, P, I64, I64, P]),
+        "amg_kcount_medians": (C.c_int, [P, P, P, P, P, I64, I64, P, P, P, I64]),
+        "amg_kcount_destroy": (C.c_int, [P]),
         "amg_nw_align": (C.c_int, [P, I32, P, I32, P, C.POINTER(I32)]),
         "amg_pop_rewrite": (C.c_int, [P, I32, I32, I64, P, P, P, P, P, I64, P, P, P, I64, P, P, P, P, P, P, P,
                                       C.POINTER(I64)]),

@@ -289,12 +289,6 @@ extern "C" int amg_get_junction_paths(amg_ctx* c, int32_t* junction_node, int8_t
 }
 
 // ------------------------------------------------------------------ the reads' bases, resident
-struct amg_seqs {
-  int device = 0;
-  DevBuf bases, off;
-  int64_t n = 0, total = 0;
-};
-
 extern "C" int amg_seqs_create(int32_t device, const char* const* seq, const int64_t* len, int64_t n, amg_seqs** out) {
   if (!out || n < 0 || (n > 0 && (!seq || !len))) return amg_fail(AMG_E_ARG, "bad argument");
   *out = nullptr;

@@ -324,6 +324,13 @@ struct amg_ctx {
   bool timing = true;
 };
 
+// the reads' bases resident in HBM (amg_seqs_create, amg_bubbles.hip; read by the path sketches and by amg_kcount.hip)
+struct amg_seqs {
+  int device = 0;
+  DevBuf bases, off;  // uint8[total + pad], int64[n + 1]
+  int64_t n = 0, total = 0;
+};
+
 // ------------------------------------------------------------------ primitives (amg_prims.hip)
 int prim_sort_u64_u32(amg_ctx* c, const unsigned long long* kin, unsigned long long* kout,
                       const unsigned int* vin, unsigned int* vout, size_t n, int end_bit);

@@ -597,3 +597,84 @@ class Sequences:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+class KmerCounts:
+    """canonical k-mer counts of resident sequences (amg_kcount_create): every window of k bases of every sequence,
+    a k-mer and its reverse complement one key — what `jellyfish count -m k -C` keeps, restated (amg_kcount.hip).
+    `sequences`: a Sequences on the engine's device, kept alive by the caller while medians() is used."""
+
+    HISTO_BINS = 10002
+
+    def __init__(self, engine, sequences, k, slots_log2=0):
+        self._h = None
+        self.engine, self.sequences = engine, sequences
+        h = C.c_void_p()
+        check(_ffi.lib.amg_kcount_create(engine._h, sequences._h, int(k), int(slots_log2), C.byref(h)))
+        self._h = h
+
+    def sizes(self):
+        """{k, windows counted, distinct keys, table slots}"""
+        out = np.zeros(4, np.int64)
+        check(_ffi.lib.amg_kcount_sizes(self._h, ptr(out)))
+        return dict(zip(("k", "windows", "distinct", "slots"), (int(x) for x in out)))
+
+    def histo(self, min_count=0):
+        """{times counted: distinct keys} without the empty bins (`jellyfish histo`: everything beyond 10 000 in bin
+        10 001); keys counted fewer than min_count times left out (`count -L`)"""
+        bins = np.zeros(self.HISTO_BINS, np.int64)
+        check(_ffi.lib.amg_kcount_histo(self.engine._h, self._h, int(min_count), ptr(bins)))
+        return {int(v): int(bins[v]) for v in np.flatnonzero(bins)}
+
+    def query(self, segments, min_count=0):
+        """per segment (str / bytes) an int64 array with one entry per base: the count of the k-mer that starts there
+        (0: absent or below min_count), -1 where no valid window starts"""
+        blobs = [s.encode() if isinstance(s, str) else bytes(s) for s in segments]
+        offs = np.zeros(len(blobs) + 1, np.int64)
+        np.cumsum([len(b) for b in blobs], out=offs[1:])
+        bases = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+        out = np.empty(len(bases), np.int64)
+        if len(bases):
+            check(_ffi.lib.amg_kcount_query(self.engine._h, self._h, ptr(bases), ptr(offs), len(blobs), int(min_count),
+                                            ptr(out)))
+        return [out[offs[i]: offs[i + 1]] for i in range(len(blobs))]
+
+    def medians(self, sets_of_rows, min_count=0, max_pairs=0):
+        """sets_of_rows: per set the rows of `sequences` it holds.  Over the counts >= max(min_count, 1) of every valid
+        window of a set's rows, in ascending order: arrays n (how many), lo (element (n - 1) // 2), hi (element n // 2).
+        A call that would make more than max_pairs counts (0: the library's limit) is refused by the library; the
+        sets are then halved until the calls pass (a single set beyond the limit raises)."""
+        sets = [np.ascontiguousarray(s, dtype=np.int64).reshape(-1) for s in sets_of_rows]
+        n, lo, hi = (np.zeros(len(sets), np.int64) for _ in range(3))
+        self._medians(sets, 0, len(sets), int(min_count), int(max_pairs), n, lo, hi)
+        return n, lo, hi
+
+    def _medians(self, sets, a, b, min_count, max_pairs, n, lo, hi):
+        if a >= b:
+            return
+        off = np.zeros(b - a + 1, np.int64)
+        np.cumsum([len(s) for s in sets[a:b]], out=off[1:])
+        rows = np.concatenate(sets[a:b]) if off[-1] else np.zeros(1, np.int64)
+        out = [np.zeros(b - a, np.int64) for _ in range(3)]
+        try:
+            check(_ffi.lib.amg_kcount_medians(self.engine._h, self._h, self.sequences._h, ptr(off), ptr(rows), b - a,
+                                              min_count, ptr(out[0]), ptr(out[1]), ptr(out[2]), max_pairs))
+        except _ffi.AmgError as e:
+            if e.code != _ffi.E_NOMEM or b - a < 2:
+                raise
+            mid = (a + b) // 2
+            self._medians(sets, a, mid, min_count, max_pairs, n, lo, hi)
+            self._medians(sets, mid, b, min_count, max_pairs, n, lo, hi)
+            return
+        n[a:b], lo[a:b], hi[a:b] = out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _ffi.lib.amg_kcount_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass

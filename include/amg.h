@@ -299,6 +299,36 @@ int amg_path_sketch_overlaps(amg_ctx* ctx, const amg_seqs* seqs, const int32_t* 
                              int64_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, int64_t* sketch_size,
                              int64_t* common);
 
+/* ---- canonical nucleotide k-mer counts (estimate_copy_numbers result_utils.py:1089-1159 and
+ *      estimate_overall_read_depth :1050-1080, which run the external tool jellyfish four times).  jellyfish's
+ *      documented behaviour is restated (amira_amd/csrc/amg_kcount.hip holds the definition): every window of k bases
+ *      of every sequence, either case, windows with a character outside ACGT skipped, none across two sequences, a
+ *      k-mer and its reverse complement one key.  k in [1, 31]; fewer than 2^32 windows (AMG_E_ARG beyond).
+ *      amg_kcount_create counts the sequences of `seqs` into an open-address table of 2^slots_log2 slots
+ *      (slots_log2 = 0: the smallest power of two >= 2 min(windows, canonical k-mers of this k)); a table that cannot
+ *      hold the keys gives AMG_E_NOMEM ("k-mer table full") and no handle.  ctx and seqs must be on one device.
+ *      amg_kcount_sizes: k, windows counted, distinct keys, slots.
+ *      amg_kcount_histo (jellyfish histo): histo[v] for 1 <= v <= 10 000 = distinct keys counted exactly v times,
+ *      histo[10 001] = those counted more often, histo[0] = 0; keys counted fewer than min_count times are left out
+ *      (count's -L; min_count <= 1: every key).
+ *      amg_kcount_query (jellyfish query -s): bases[seg_off[s] .. seg_off[s + 1]) is sequence s (HOST arrays, as
+ *      amg_minhash takes them); out_count has one entry per BASE: the count of the k-mer that starts there (0 for a key
+ *      that is absent or below min_count), -1 where no valid window starts.
+ *      amg_kcount_medians: set s holds the rows set_row[set_off[s] .. set_off[s + 1]) of `seqs` (a row may be in
+ *      several sets).  Over the counts >= max(min_count, 1) of all valid windows of a set's rows, one per occurrence,
+ *      in ascending order: n[s] = how many, mid_lo[s] = element (n - 1) / 2, mid_hi[s] = element n / 2 (0, 0, 0 for
+ *      an empty list).  More than max_pairs counts in one call (<= 0: 2^30) give AMG_E_NOMEM: split the sets. --- */
+typedef struct amg_kcount amg_kcount;
+int amg_kcount_create(amg_ctx* ctx, const amg_seqs* seqs, int32_t k, int32_t slots_log2, amg_kcount** out);
+int amg_kcount_sizes(const amg_kcount* counts, int64_t sizes[4]);
+int amg_kcount_histo(amg_ctx* ctx, const amg_kcount* counts, int64_t min_count, int64_t histo[10002]);
+int amg_kcount_query(amg_ctx* ctx, const amg_kcount* counts, const uint8_t* bases, const int64_t* seg_off,
+                     int64_t n_seg, int64_t min_count, int64_t* out_count);
+int amg_kcount_medians(amg_ctx* ctx, const amg_kcount* counts, const amg_seqs* seqs, const int64_t* set_off,
+                       const int64_t* set_row, int64_t n_sets, int64_t min_count, int64_t* n, int64_t* mid_lo,
+                       int64_t* mid_hi, int64_t max_pairs);
+int amg_kcount_destroy(amg_kcount* counts);
+
 /* needleman_wunsch (construct_graph.py:1433-1480) of two short lists of interned genes on the host: match 1, mismatch 0,
  * gap -1, ties UP > LEFT > DIAG as the reference's max over (score, pointer) gives them.  ops (room for n + m), in
  * alignment order: 0 = (x gene, y gene), 1 = (x gene, "*"), 2 = ("*", y gene). */
