@@ -61,3 +61,112 @@ def test_reference_held_containments_through_the_product():
         assert len(m1 & m2) / len(m2) == 0.9091323161011159
         checked += 1
     assert checked == 1
+
+
+# ------------------------------------------------------------------ segment boundaries against the tiles of k_minhash
+TILE = 1024    # MH_TILE: k-mer starts per workgroup
+
+
+def _compare(segs, ksize, scaled=1):
+    """every segment a sketch of its own, on the device and by the oracle; returns the number of hashes compared"""
+    import path_sketch as PS
+    from amira_amd import Engine
+    eng = Engine(0)
+    try:
+        got = eng.minhash(segs, list(range(len(segs))), ksize, scaled)
+    finally:
+        eng.close()
+    assert sorted(got) == list(range(len(segs)))
+    for s, seg in enumerate(segs):
+        assert got[s] == set(PS.sketch(seg, ksize, scaled)), (s, len(seg), ksize)
+    return sum(len(v) for v in got.values())
+
+
+def _cut(text, cuts):
+    cuts = [0] + sorted(set(cuts)) + [len(text)]
+    return [text[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
+@pytest.mark.parametrize("ksize", [1, 8, 11, 17, 32])
+def test_segment_boundaries_on_the_edges_of_a_tile(ksize):
+    """boundaries at stream offsets 1023, 1024, 1025, 2048 - ksize and 2048 - ksize + 1, and a segment whose last window
+    ends on the last base of a tile (it ends at 2048); no window may run from one segment into the next"""
+    import path_sketch as PS
+    rng = np.random.default_rng(500 + ksize)
+    text = PS.bases(rng, 3 * TILE + 77)
+    segs = _cut(text, [1023, 1024, 1025, 2 * TILE - ksize, 2 * TILE - ksize + 1, 2 * TILE, 3 * TILE - 1])
+    assert np.cumsum([len(s) for s in segs])[:-1].tolist() == sorted({1023, 1024, 1025, 2048 - ksize, 2049 - ksize, 2048, 3071})
+    assert _compare(segs, ksize) > 0
+    # the same bases as ONE segment have more windows than the pieces: those across the cuts
+    assert len(PS.sketch(text, ksize, 1)) > len(set().union(*[PS.sketch(s, ksize, 1) for s in segs])) or ksize == 1
+
+
+@pytest.mark.parametrize("ksize", [2, 3, 11])
+def test_hundreds_of_tiny_segments_in_one_tile_before_a_long_one(ksize):
+    import path_sketch as PS
+    rng = np.random.default_rng(600 + ksize)
+    segs = [PS.bases(rng, n) for n in rng.choice(4, 700, p=[0.3, 0.3, 0.2, 0.2])]
+    assert sum(len(s) for s in segs) < TILE and {len(s) for s in segs} == {0, 1, 2, 3}
+    segs.append(PS.bases(rng, 1500))
+    assert _compare(segs, ksize) > 10
+
+
+@pytest.mark.parametrize("ksize", [4, 11])
+def test_runs_of_empty_segments_on_a_tile_edge_and_at_the_end(ksize):
+    import path_sketch as PS
+    rng = np.random.default_rng(700 + ksize)
+    segs = [""] * 3 + [PS.bases(rng, TILE)] + [""] * 20 + [PS.bases(rng, 700)] + [""] * 70 + [PS.bases(rng, 324 + TILE)] + [""] * 5
+    assert _compare(segs, ksize) > 300
+
+
+@pytest.mark.parametrize("n", [TILE, TILE + 1])
+@pytest.mark.parametrize("ksize", [1, 11, 32])
+def test_a_stream_of_one_tile_and_of_one_base_more(n, ksize):
+    import path_sketch as PS
+    rng = np.random.default_rng(800 + n + ksize)
+    text = PS.bases(rng, n)
+    assert _compare([text], ksize) > 0
+    assert _compare([text[:1000], text[1000:]], ksize) > 0
+
+
+def test_capacity_smaller_than_the_result_and_null_outputs():
+    """include/amg.h: out_set / out_hash may be NULL to get the count only; with a cap below the count the count is the
+    same and nothing is written behind cap"""
+    import ctypes as C
+    from collections import Counter
+    import path_sketch as PS
+    from amira_amd import Engine, _ffi
+    from amira_amd._ffi import check, ptr
+    ksize, scaled = 11, 3
+    rng = np.random.default_rng(900)
+    segs = [PS.bases(rng, n) for n in (700, 0, 1024, 5, 1300)] + ["ACGTTGCAAGTC" * 40]   # (the last: hashes many times over)
+    sets = np.array([0, 1, 2, 2, 0, 3], np.int32)
+    offs = np.zeros(len(segs) + 1, np.int64)
+    np.cumsum([len(s) for s in segs], out=offs[1:])
+    stream = np.frombuffer("".join(segs).encode(), np.uint8)
+    want = Counter((int(sets[i]), h) for i, seg in enumerate(segs) for j in range(len(seg) - ksize + 1)
+                   for h in PS.sketch(seg[j:j + ksize], ksize, scaled))
+    total = sum(want.values())
+    assert total > len(want) > 500
+    GUARD_S, GUARD_H = np.int32(-77), np.uint64(0xDEADBEEFDEADBEEF)
+    eng = Engine(0)
+    try:
+        def run(cap, with_outputs=True):
+            o_set, o_hash = np.full(cap + 8, GUARD_S, np.int32), np.full(cap + 8, GUARD_H, np.uint64)
+            n = C.c_int64(-1)
+            check(_ffi.lib.amg_minhash(eng._h, ptr(stream), ptr(offs), ptr(sets), len(segs), ksize, scaled,
+                                       ptr(o_set) if with_outputs else None, ptr(o_hash) if with_outputs else None, cap,
+                                       C.byref(n)))
+            return n.value, o_set, o_hash
+        assert run(0, False)[0] == total
+        assert run(total, False)[0] == total           # (a cap without outputs is not a promise of room)
+        for cap in (total, total - 1, 1, total + 5):
+            n, o_set, o_hash = run(cap)
+            assert n == total, cap
+            m = min(cap, total)
+            got = Counter(zip(o_set[:m].tolist(), o_hash[:m].tolist()))
+            assert not got - want, (cap, "pairs that are not among the expected ones")
+            assert cap < total or got == want
+            assert (o_set[m:] == GUARD_S).all() and (o_hash[m:] == GUARD_H).all(), cap
+    finally:
+        eng.close()
