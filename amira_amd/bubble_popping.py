@@ -3,7 +3,8 @@ amira/construct_graph.py (reference v0.11.0): correct_low_coverage_paths :2196-2
 callees (:1482-1485, :1515-1667, :1693-1955, :1977-2014, :2066-2194, :2252-2265), plus
 get_unitigs_in_graph :2961-2975 (row f4).
 
-What grows with the data runs on the device, on the device's own node ids (amira_amd/csrc/amg_bubbles.hip):
+What grows with the data runs on the device, on the device's own node ids (amira_amd/csrc/amg_bubbles.hip for the
+first, amg_sketch.hip for the second):
   * the search for the paths between junctions — ONE search per start junction that notes every junction it arrives at,
     where the reference searches once per (start, stop) pair (`Engine.junction_paths`);
   * the sketches: the reads' bases are uploaded once per cleaning run (`Sequences`), a node's sketch is hashed straight

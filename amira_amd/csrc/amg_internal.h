@@ -153,6 +153,7 @@ static inline int overflowed(Overflow* which, Overflow cause) { return *which = 
 
 struct DistState;  // amg_dist.h: communicator, buffers and progress of the ctx's merged builds
 struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until the caller has fetched it
+struct SketchState;  // amg_sketch.hip: the buffers of amg_path_sketch_overlaps
 struct PopState;     // amg_pop.hip: the buffers of amg_pop_rewrite
 
 struct amg_ctx {
@@ -276,6 +277,7 @@ struct amg_ctx {
   uint32_t dist_min_node = 1, dist_min_edge = 1;  // fused filter of the next merged build
   DistState* dist = nullptr;
   BubbleState* bub = nullptr;  // amg_bubbles.hip
+  SketchState* sk = nullptr;   // amg_sketch.hip
   PopState* pop = nullptr;     // amg_pop.hip
 
   // ---- K6 result cache (two-call protocol of amg_match_patterns)
@@ -324,7 +326,7 @@ struct amg_ctx {
   bool timing = true;
 };
 
-// the reads' bases resident in HBM (amg_seqs_create, amg_bubbles.hip; read by the path sketches and by amg_kcount.hip)
+// the reads' bases resident in HBM (amg_seqs_create, amg_sketch.hip; read by the path sketches and by amg_kcount.hip)
 struct amg_seqs {
   int device = 0;
   DevBuf bases, off;  // uint8[total + pad], int64[n + 1]
@@ -421,7 +423,8 @@ struct GView {
 };
 int ensure_live_adj(amg_ctx* c);  // the live lists below exist and are up to date
 GView make_view(amg_ctx* c);
-void bubbles_release(amg_ctx* c);
+void bubbles_release(amg_ctx* c);  // amg_bubbles.hip
+void sketch_release(amg_ctx* c);   // amg_sketch.hip
 void pop_release(amg_ctx* c);  // amg_pop.hip
 
 void dist_release(amg_ctx* c);  // amg_dist.hip

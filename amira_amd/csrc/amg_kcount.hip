@@ -3,7 +3,7 @@
 // from four calls of the external tool jellyfish.
 //
 // jellyfish is not part of the reference's tree, and it exists neither where this unit is built nor where it runs, so
-// what follows RESTATES its documented behaviour (as amg_minhash.hip restates sourmash's) and nobody has checked the
+// what follows RESTATES its documented behaviour (as amg_sketch.hip restates sourmash's) and nobody has checked the
 // restatement against the tool itself:
 //   count -m k -C   every window of k bases of every sequence is counted, upper and lower case alike; a window that
 //                   holds a character outside ACGT is skipped; no window spans two sequences; a k-mer and its reverse
@@ -18,13 +18,13 @@
 // Every probe loop is bounded by the number of slots; an insert that finds no place raises a status word and the call
 // fails with AMG_E_NOMEM ("k-mer table full") instead of spinning.
 //
-// All kernels walk a stream of bases in k_minhash's tiles: 1024 window starts + a k - 1 halo staged once in LDS
-// (km_stage), the tile's sequences found by two searches per block, every thread's k-mer cut out of LDS as words
-// (amg_kmer.h) and packed to two bits per base: (c >> 1) & 3 gives A 0, C 1, T 2, G 3, and the complement is ^ 2.
+// Insert, query and emit walk their bases with base_tile (amg_bases.h: the stream, the tile, the search, the
+// compaction of k_kc_emit's records); their key is kc_key: the k-mer cut out of LDS as words and packed to two bits
+// per base, (c >> 1) & 3 gives A 0, C 1, T 2, G 3, and the complement is ^ 2.  This unit holds that key, the table
+// (kc_upsert, kc_find), the tally, the histogram, the medians' pick and the host calls.
 // Traffic of the count pass: 1 byte per base read (a stream) + one 64-byte sector per probe + one per add (random).
-#include "amg_kmer.h"
+#include "amg_bases.h"
 
-#define KC_TILE 1024
 #define KC_MAX_K 31
 #define KC_EMPTY (~0ull)
 #define KC_BINS 10002  // bins 0 .. 10 001 of a histogram (bin 0 stays empty)
@@ -36,16 +36,6 @@ struct amg_kcount {
   DevBuf keys, counts;  // uint64[slots], uint32[slots]
   // scratch of amg_kcount_medians (the handle is const to its readers; a ctx is not thread-safe, nor is this)
   mutable DevBuf m_row, m_set, m_len, m_src, m_off, m_key, m_srt, m_v0, m_v1, m_out;
-};
-
-// a stream of bases cut into segments: segment s is stream[seg_off[s] .. seg_off[s + 1]) and lies at
-// bases[seg_src[s] ..] (seg_src == nullptr: the stream is `bases` itself)
-struct KcSrc {
-  const unsigned char* bases;
-  long long n_bases;
-  const long long* seg_off;
-  long long n_seg;
-  const long long* seg_src;
 };
 
 // eight staged bases (a byte each) -> sixteen bits, first base lowest
@@ -74,60 +64,6 @@ __device__ __forceinline__ bool kc_key(const unsigned char* lds, int i, int k, u
   r = (r >> sh) ^ (0xAAAAAAAAAAAAAAAAull >> sh);
   *key = x < r ? x : r;
   return true;
-}
-
-// Stages the tile that starts at stream position t0 and gives every thread its four windows (starts t0 + threadIdx.x
-// + 256 it): whether a valid window starts there, its key and its segment.  All 256 threads call.
-template <int NW>
-__device__ __forceinline__ void kc_tile(const KcSrc& s, int k, long long t0, unsigned char* s_b, long long* s_seg,
-                                        bool (&valid)[4], unsigned long long (&key)[4], long long (&seg)[4]) {
-  if (threadIdx.x < 2) {
-    const long long t = threadIdx.x == 0 ? t0 : (t0 + KC_TILE - 1 < s.n_bases ? t0 + KC_TILE - 1 : s.n_bases - 1);
-    long long lo = 0, hi = s.n_seg;  // seg_off[lo] <= t < seg_off[hi]
-    while (hi - lo > 1) {
-      const long long mid = (lo + hi) >> 1;
-      if (s.seg_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    s_seg[threadIdx.x] = lo;
-  }
-  __syncthreads();
-  const long long seg_lo = s_seg[0], seg_hi = s_seg[1] + 1;
-  for (int i = threadIdx.x; i < KC_TILE + KM_MAX_K + 24; i += 256) {
-    const long long t = t0 + i;
-    unsigned char b = 0;
-    if (i < KC_TILE + k - 1 && t < s.n_bases) {
-      if (s.seg_src == nullptr) {
-        b = km_stage(s.bases[t]);
-      } else {
-        long long lo = seg_lo, hi = seg_hi;
-        while (hi - lo > 1) {
-          const long long mid = (lo + hi) >> 1;
-          if (s.seg_off[mid] <= t) lo = mid; else hi = mid;
-        }
-        // (a halo byte behind the tile's last segment belongs to no window that starts in this tile)
-        if (t < s.seg_off[lo + 1]) b = km_stage(s.bases[s.seg_src[lo] + (t - s.seg_off[lo])]);
-      }
-    }
-    s_b[i] = b;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int i = threadIdx.x + it * 256;
-    const long long t = t0 + i;
-    valid[it] = false;
-    key[it] = 0ull;
-    seg[it] = 0;
-    if (t + k > s.n_bases) continue;
-    long long lo = seg_lo, hi = seg_hi;
-    while (hi - lo > 1) {
-      const long long mid = (lo + hi) >> 1;
-      if (s.seg_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    seg[it] = lo;
-    if (t + k > s.seg_off[lo + 1]) continue;  // the window runs over the end of its sequence
-    valid[it] = kc_key<NW>(s_b, i, k, &key[it]);
-  }
 }
 
 // `add` occurrences of `key` into the table.  The slot's key is read with a plain load first: at sequencing depth
@@ -170,95 +106,71 @@ __device__ __forceinline__ unsigned int kc_find(const unsigned long long* __rest
 // consecutive windows: the first lane of every run of equal keys adds the run's length, the others add nothing
 // (tens of thousands of adds on one word would otherwise queue up at the rate one word takes them).
 template <int NW, bool FOLD>
-__global__ __launch_bounds__(256) void k_kc_insert(KcSrc s, int k, unsigned long long* keys, unsigned int* counts,
+__global__ __launch_bounds__(256) void k_kc_insert(BaseStream s, int k, unsigned long long* keys, unsigned int* counts,
                                                    unsigned long long mask, unsigned long long* full) {
-  __shared__ __attribute__((aligned(8))) unsigned char s_b[KC_TILE + KM_MAX_K + 24];
-  __shared__ long long s_seg[2];
-  bool valid[4];
-  unsigned long long key[4];
-  long long seg[4];
-  kc_tile<NW>(s, k, (long long)blockIdx.x * KC_TILE, s_b, s_seg, valid, key, seg);
+  BaseWin w;
+  base_tile<false, kc_key<NW>>(s, k, (long long)blockIdx.x * BT_TILE, w);
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-    unsigned int add = valid[it] ? 1u : 0u;
+    unsigned int add = w.valid[it] ? 1u : 0u;
     if (FOLD) {
-      const unsigned long long prev = (unsigned long long)__shfl_up((long long)key[it], 1, 64);
-      const int prev_valid = __shfl_up((int)valid[it], 1, 64);
-      const bool head = valid[it] && (lane == 0 || !prev_valid || prev != key[it]);
-      const unsigned long long heads = __ballot(head), live = __ballot(valid[it]);
+      const unsigned long long prev = (unsigned long long)__shfl_up((long long)w.key[it], 1, 64);
+      const int prev_valid = __shfl_up((int)w.valid[it], 1, 64);
+      const bool head = w.valid[it] && (lane == 0 || !prev_valid || prev != w.key[it]);
+      const unsigned long long heads = __ballot(head), live = __ballot(w.valid[it]);
       // the run of a head ends before the next head or the next lane without a window
       const unsigned long long stop = (heads | ~live) & ~((2ull << lane) - 1ull);
       const int end = stop ? __ffsll((long long)stop) - 1 : 64;
       add = head ? (unsigned int)(end - lane) : 0u;
     }
-    if (add) kc_upsert(keys, counts, mask, key[it], add, full);
+    if (add) kc_upsert(keys, counts, mask, w.key[it], add, full);
   }
 }
 
 // out[t] = count of the k-mer that starts at stream position t (0: absent or below min_count), -1: no valid window
 template <int NW>
-__global__ __launch_bounds__(256) void k_kc_query(KcSrc s, int k, const unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(256) void k_kc_query(BaseStream s, int k, const unsigned long long* __restrict__ keys,
                                                   const unsigned int* __restrict__ counts, unsigned long long mask,
                                                   unsigned int min_count, long long* __restrict__ out) {
-  __shared__ __attribute__((aligned(8))) unsigned char s_b[KC_TILE + KM_MAX_K + 24];
-  __shared__ long long s_seg[2];
-  bool valid[4];
-  unsigned long long key[4];
-  long long seg[4];
-  const long long t0 = (long long)blockIdx.x * KC_TILE;
-  kc_tile<NW>(s, k, t0, s_b, s_seg, valid, key, seg);
+  const long long t0 = (long long)blockIdx.x * BT_TILE;
+  BaseWin w;
+  base_tile<false, kc_key<NW>>(s, k, t0, w);
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const long long t = t0 + threadIdx.x + it * 256;
     if (t >= s.n_bases) continue;
     long long v = -1;
-    if (valid[it]) {
-      const unsigned int cnt = kc_find(keys, counts, mask, key[it]);
+    if (w.valid[it]) {
+      const unsigned int cnt = kc_find(keys, counts, mask, w.key[it]);
       v = cnt >= min_count ? (long long)cnt : 0ll;
     }
     out[t] = v;
   }
 }
 
-// (set << 32 | count) of every valid window whose count is >= min_count (>= 1), unordered; places from a block scan
-// and one atomicAdd per block; nothing is written at or beyond cap, *counter says how many there were
+// (set << 32 | count) of every valid window of a GATHERED stream whose count is >= min_count (>= 1), unordered
+// (block_emit: nothing is written at or beyond cap, *counter says how many there were)
 template <int NW>
-__global__ __launch_bounds__(256) void k_kc_emit(KcSrc s, int k, const unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(256) void k_kc_emit(BaseStream s, int k, const unsigned long long* __restrict__ keys,
                                                  const unsigned int* __restrict__ counts, unsigned long long mask,
                                                  unsigned int min_count, const int* __restrict__ seg_set,
                                                  unsigned long long* counter, long long cap,
                                                  unsigned long long* __restrict__ out) {
-  __shared__ __attribute__((aligned(8))) unsigned char s_b[KC_TILE + KM_MAX_K + 24];
-  __shared__ long long s_seg[2];
-  __shared__ unsigned int s_wave[4];
-  __shared__ unsigned long long s_base;
-  bool valid[4];
-  unsigned long long key[4];
-  long long seg[4];
-  kc_tile<NW>(s, k, (long long)blockIdx.x * KC_TILE, s_b, s_seg, valid, key, seg);
+  BaseWin w;
+  base_tile<true, kc_key<NW>>(s, k, (long long)blockIdx.x * BT_TILE, w);
   unsigned long long rec[4];
   unsigned int keep = 0;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-    if (!valid[it]) continue;
-    const unsigned int cnt = kc_find(keys, counts, mask, key[it]);
+    if (!w.valid[it]) continue;
+    const unsigned int cnt = kc_find(keys, counts, mask, w.key[it]);
     if (cnt >= min_count) {
-      rec[it] = ((unsigned long long)(unsigned int)seg_set[seg[it]] << 32) | cnt;
+      rec[it] = ((unsigned long long)(unsigned int)seg_set[w.seg[it]] << 32) | cnt;
       keep |= 1u << it;
     }
   }
-  unsigned int total;
-  const unsigned int off = block_exscan_256((unsigned int)__popc(keep), &total, s_wave);
-  if (threadIdx.x == 0) s_base = total ? atomicAdd(counter, (unsigned long long)total) : 0ull;
-  __syncthreads();
-  unsigned long long o = s_base + off;
-#pragma unroll
-  for (int it = 0; it < 4; ++it)
-    if (keep & (1u << it)) {
-      if ((long long)o < cap) out[o] = rec[it];
-      ++o;
-    }
+  block_emit(keep, counter, cap, [&](unsigned long long o, int it) { out[o] = rec[it]; });
 }
 
 // sum over the sequences of the windows they can hold: max(len - k + 1, 0)
@@ -370,8 +282,6 @@ static unsigned int kc_grid(long long n) {
   return (unsigned int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
 
-#define KC_BY_WORDS(k, K) ((k) <= 8 ? K(1) : (k) <= 16 ? K(2) : (k) <= 24 ? K(3) : K(4))
-
 extern "C" int amg_kcount_create(amg_ctx* c, const amg_seqs* seqs, int32_t k, int32_t slots_log2, amg_kcount** out) {
   if (!c || !seqs || !out) return amg_fail(AMG_E_ARG, "null argument");
   *out = nullptr;
@@ -419,13 +329,11 @@ extern "C" int amg_kcount_create(amg_ctx* c, const amg_seqs* seqs, int32_t k, in
   if (bound > 0) {
     const char* sw = getenv("AMG_KCOUNT_FOLD");  // A/B switch: 0 = one add per window
     const bool fold = !(sw && sw[0] == '0');
-    const KcSrc src{seqs->bases.as<unsigned char>(), (long long)seqs->total, seqs->off.as<long long>(),
-                    (long long)seqs->n, nullptr};
+    const BaseStream src{seqs->bases.as<unsigned char>(), (long long)seqs->total, seqs->off.as<long long>(),
+                         (long long)seqs->n, nullptr};
     stage_begin(c, "kcount_insert");
-#define KC_INS(NW) (fold ? k_kc_insert<NW, true> : k_kc_insert<NW, false>)
-    auto kern = KC_BY_WORDS(k, KC_INS);
-#undef KC_INS
-    hipLaunchKernelGGL(kern, dim3(nblk(seqs->total, KC_TILE)), dim3(256), 0, st, src, (int)k,
+    auto kern = KM_BY_WORDS(k, (fold ? &k_kc_insert<NW, true> : &k_kc_insert<NW, false>));
+    hipLaunchKernelGGL(kern, dim3(nblk(seqs->total, BT_TILE)), dim3(256), 0, st, src, (int)k,
                        h->keys.as<unsigned long long>(), h->counts.as<unsigned int>(), (unsigned long long)(slots - 1),
                        word + 2);
     stage_end(c);
@@ -496,9 +404,7 @@ extern "C" int amg_kcount_query(amg_ctx* c, const amg_kcount* h, const uint8_t* 
   if (h->device != c->device) return amg_fail(AMG_E_ARG, "the k-mer table lives on another device");
   if (n_seg < 0 || (n_seg > 0 && !seg_off)) return amg_fail(AMG_E_ARG, "bad segments");
   if (n_seg == 0) return AMG_OK;
-  if (seg_off[0] != 0) return amg_fail(AMG_E_ARG, "seg_off[0] must be 0");
-  for (int64_t s = 0; s < n_seg; ++s)
-    if (seg_off[s + 1] < seg_off[s]) return amg_fail(AMG_E_ARG, "seg_off not monotone");
+  AMGCHK(offsets_check(seg_off, n_seg, "seg_off[0] must be 0", "seg_off not monotone"));
   const int64_t n_bases = seg_off[n_seg];
   if (n_bases == 0) return AMG_OK;
   if (!bases || !out_count) return amg_fail(AMG_E_ARG, "null argument");
@@ -512,11 +418,8 @@ extern "C" int amg_kcount_query(amg_ctx* c, const amg_kcount* h, const uint8_t* 
   HIPCHK(hipMemcpyAsync(d_off.p, seg_off, (size_t)(n_seg + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
   stages_reset(c);
   stage_begin(c, "kcount_query");
-  const KcSrc src{d_b.as<unsigned char>(), (long long)n_bases, d_off.as<long long>(), (long long)n_seg, nullptr};
-#define KC_QRY(NW) k_kc_query<NW>
-  auto kern = KC_BY_WORDS(h->k, KC_QRY);
-#undef KC_QRY
-  hipLaunchKernelGGL(kern, dim3(nblk(n_bases, KC_TILE)), dim3(256), 0, st, src, (int)h->k,
+  const BaseStream src{d_b.as<unsigned char>(), (long long)n_bases, d_off.as<long long>(), (long long)n_seg, nullptr};
+  hipLaunchKernelGGL(KM_BY_WORDS(h->k, &k_kc_query<NW>), dim3(nblk(n_bases, BT_TILE)), dim3(256), 0, st, src, (int)h->k,
                      h->keys.as<unsigned long long>(), h->counts.as<unsigned int>(), (unsigned long long)(h->slots - 1),
                      kc_min_count(min_count), d_out.as<long long>());
   stage_end(c);
@@ -535,9 +438,8 @@ extern "C" int amg_kcount_medians(amg_ctx* c, const amg_kcount* h, const amg_seq
     return amg_fail(AMG_E_ARG, "bad sets");
   if (n_sets == 0) return AMG_OK;
   const int64_t P = set_off[n_sets];
-  if (set_off[0] != 0 || (P > 0 && !set_row)) return amg_fail(AMG_E_ARG, "bad set offsets");
-  for (int64_t s = 0; s < n_sets; ++s)
-    if (set_off[s + 1] < set_off[s]) return amg_fail(AMG_E_ARG, "set offsets not monotone");
+  if (P > 0 && !set_row) return amg_fail(AMG_E_ARG, "bad set offsets");
+  AMGCHK(offsets_check(set_off, n_sets, "bad set offsets", "set offsets not monotone"));
   for (int64_t p = 0; p < P; ++p)
     if (set_row[p] < 0 || set_row[p] >= seqs->n)
       return amg_fail(AMG_E_ARG, "set row %lld is not a sequence", (long long)set_row[p]);
@@ -574,11 +476,9 @@ extern "C" int amg_kcount_medians(amg_ctx* c, const amg_kcount* h, const amg_seq
   // a window per base at most: room for all of them, or for as many as one call may make
   const long long cap = V < max_pairs ? V : max_pairs;
   AMGCHK(h->m_key.ensure((size_t)(cap + 1) * sizeof(unsigned long long)));
-  const KcSrc src{seqs->bases.as<unsigned char>(), V, h->m_off.as<long long>(), (long long)P, h->m_src.as<long long>()};
-#define KC_EMT(NW) k_kc_emit<NW>
-  auto kern = KC_BY_WORDS(h->k, KC_EMT);
-#undef KC_EMT
-  hipLaunchKernelGGL(kern, dim3(nblk(V, KC_TILE)), dim3(256), 0, st, src, (int)h->k, h->keys.as<unsigned long long>(),
+  const BaseStream src{seqs->bases.as<unsigned char>(), V, h->m_off.as<long long>(), (long long)P,
+                       h->m_src.as<long long>()};
+  hipLaunchKernelGGL(KM_BY_WORDS(h->k, &k_kc_emit<NW>), dim3(nblk(V, BT_TILE)), dim3(256), 0, st, src, (int)h->k, h->keys.as<unsigned long long>(),
                      h->counts.as<unsigned int>(), (unsigned long long)(h->slots - 1), kc_min_count(min_count),
                      h->m_set.as<int>(), counter, cap, h->m_key.as<unsigned long long>());
   unsigned long long M = 0;

@@ -1,4 +1,4 @@
-"""Constructed read sets for amg_path_sketch_overlaps (amira_amd/csrc/amg_bubbles.hip: k_bs_mark, k_bs_fill, k_bs_segs,
+"""Constructed read sets for amg_path_sketch_overlaps (amira_amd/csrc/amg_sketch.hip: k_bs_mark, k_bs_fill, k_bs_segs,
 k_bs_hash, k_bs_unique, k_bs_pstart, k_bs_common) and the numbers the reference gives on each, for
 tests/test_path_sketch_cpu.py (the cases against the reference alone) and tests/test_gpu_path_sketch.py.
 

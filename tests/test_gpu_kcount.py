@@ -240,6 +240,92 @@ def test_medians_of_read_sets(eng):
         close(kc, resident)
 
 
+# ------------------------------------------------------------------ sequence boundaries against the tiles of base_tile
+TILE = 1024    # BT_TILE (amg_bases.h): window starts per workgroup
+
+
+def _cut(text, cuts):
+    cuts = [0] + sorted(set(cuts)) + [len(text)]
+    return [text[a:b] for a, b in zip(cuts, cuts[1:])]
+
+
+@pytest.mark.parametrize("k", [1, 8, 9, 16, 17, 31])   # (either side of every step of the words per k-mer)
+def test_query_across_tile_seams(eng, k):
+    """host segments, nothing gathered: the cuts of test_gpu_minhash.py's
+    test_segment_boundaries_on_the_edges_of_a_tile.  The table holds the UNCUT text, so a window that ran over a cut
+    would be found in it"""
+    text = acgt(np.random.default_rng(1100 + k), 3 * TILE + 77)
+    pieces = _cut(text, [1023, 1024, 1025, 2 * TILE - k, 2 * TILE - k + 1, 2 * TILE, 3 * TILE - 1])
+    assert np.cumsum([len(s) for s in pieces])[:-1].tolist() == sorted({1023, 1024, 1025, 2048 - k, 2049 - k, 2048, 3071})
+    table = O.Table([text], k)
+    kc, resident = counted(eng, [text], k)
+    try:
+        got = kc.query(pieces)
+        for piece, g in zip(pieces, got):
+            want = table.lookup(piece)
+            assert np.array_equal(g == -1, want == -1), (k, len(piece))
+            assert np.array_equal(g, want), (k, len(piece))
+        whole = kc.query([text])[0]
+        assert np.array_equal(whole, table.lookup(text))
+        windows, uncut = sum(int((g != -1).sum()) for g in got), int((whole != -1).sum())
+        assert uncut == len(text) - k + 1 and (windows < uncut if k > 1 else windows == uncut)
+    finally:
+        close(kc, resident)
+
+
+@functools.lru_cache(maxsize=None)
+def gather_case():
+    """rows cut out of one text so that the rows listed side by side in a set are neighbours in the text too, and
+    another row covers the place where they meet: a window that ran from one row into the next would be counted"""
+    lengths = [1023, 1, 0, 1024, 1025, 700, 0, 0, 324 + 1024, 5]
+    starts = [1025, 1947, 0, 2048, 0, 1700, 0, 0, 600, 2046]
+    text = acgt(np.random.default_rng(1200), 3 * TILE + 77)
+    rows = [text[a: a + n] for a, n in zip(starts, lengths)]
+    sets = [[4, 0, 3], [8, 8, 1], [2, 6, 7], [9, 5, 4, 3, 0]]
+    return text, rows, sets
+
+
+@pytest.mark.parametrize("k", [3, 15])
+def test_medians_through_the_gather_across_tile_seams(eng, k):
+    text, rows, sets = gather_case()
+    # the stream the kernel walks: the listed rows of all sets end to end
+    ends = np.cumsum([len(rows[r]) for rows_of in sets for r in rows_of]).tolist()
+    assert {1023, 1024, 1025} & set(ends) and any(e > 0 and e % TILE == 0 for e in ends)   # (a row's last base = a tile's)
+    assert ends.count(ends[5]) > 1                                                          # empty rows in the stream
+    table = O.Table(rows, k)
+    # rows 4 | 0 | 3 of the first set meet at 1025 and 2048 of the text: the windows across are in the table (rows 8, 5)
+    assert (table.lookup(text[1025 - k + 1: 1025 + k - 1])[: k - 1] > 0).all()
+    assert (table.lookup(text[2048 - k + 1: 2048 + k - 1])[: k - 1] > 0).all()
+    kc, resident = counted(eng, rows, k)
+    try:
+        for m in (0, 2):
+            want = want_medians(table, rows, sets, m)
+            n, lo, hi = kc.medians(sets, m)
+            assert (n.tolist(), lo.tolist(), hi.tolist()) == want, (k, m)
+        assert want_medians(table, rows, sets, 0)[0][2] == 0 and min(want_medians(table, rows, sets, 0)[0][:2]) > 2000
+    finally:
+        close(kc, resident)
+
+
+@pytest.mark.parametrize("k", [2, 3])
+def test_hundreds_of_tiny_rows_in_one_tile_before_a_long_one(eng, k):
+    """test_gpu_minhash.py's case of the same name through the other two entries: every thread's search goes over
+    hundreds of offsets"""
+    rng = np.random.default_rng(1300 + k)
+    rows = [acgt(rng, n) for n in rng.choice(4, 700, p=[0.3, 0.3, 0.2, 0.2])]
+    assert sum(len(s) for s in rows) < TILE and {len(s) for s in rows} == {0, 1, 2, 3}
+    rows.append(acgt(rng, 1500))
+    kc, resident = counted(eng, rows, k)
+    try:
+        table = check_against_oracle(kc, rows, k)
+        sets = [list(range(len(rows)))]
+        want = want_medians(table, rows, sets, 0)
+        n, lo, hi = kc.medians(sets)
+        assert (n.tolist(), lo.tolist(), hi.tolist()) == want and want[0][0] == table.windows > 1500 - k
+    finally:
+        close(kc, resident)
+
+
 def test_a_call_refused_for_its_size_is_halved(eng):
     from amira_amd._ffi import AmgError, E_NOMEM
     from amira_amd.engine import KmerCounts

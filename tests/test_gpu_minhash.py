@@ -19,7 +19,7 @@ def _random_segments(rng, n, lo, hi):
 
 
 @pytest.mark.parametrize("ksize,scaled", [(11, 10), (9, 1), (21, 3), (4, 1), (32, 2),
-                                          (1, 1), (8, 1), (16, 1), (17, 1), (24, 2), (25, 1), (31, 1)])   # (word boundaries of amg_kmer.h)
+                                          (1, 1), (8, 1), (16, 1), (17, 1), (24, 2), (25, 1), (31, 1)])   # (word boundaries of amg_bases.h)
 def test_device_sketch_equals_oracle(ksize, scaled):
     from amira_amd import Engine
     from amira_oracle.minhash import MinHash
@@ -64,7 +64,7 @@ def test_reference_held_containments_through_the_product():
 
 
 # ------------------------------------------------------------------ segment boundaries against the tiles of k_minhash
-TILE = 1024    # MH_TILE: k-mer starts per workgroup
+TILE = 1024    # BT_TILE (amg_bases.h): k-mer starts per workgroup
 
 
 def _compare(segs, ksize, scaled=1):
@@ -99,6 +99,22 @@ def test_segment_boundaries_on_the_edges_of_a_tile(ksize):
     assert _compare(segs, ksize) > 0
     # the same bases as ONE segment have more windows than the pieces: those across the cuts
     assert len(PS.sketch(text, ksize, 1)) > len(set().union(*[PS.sketch(s, ksize, 1) for s in segs])) or ksize == 1
+
+
+@pytest.mark.parametrize("scaled", [1, 2, 10, 2048, 2 ** 63])
+def test_the_scaled_cut_is_the_oracles(scaled):
+    """km_max_hash (amg_bases.h) through a sketch: the hashes kept are those at or below the oracle's max_hash"""
+    import path_sketch as PS
+    from amira_oracle.minhash import max_hash_for_scaled
+    assert [max_hash_for_scaled(s) for s in (1, 2, 10, 2048, 2 ** 63)] == [2 ** 64 - 1, 2 ** 63, 1844674407370955264,
+                                                                            2 ** 53, 2]
+    kept = _compare([PS.bases(np.random.default_rng(550), 20000)], 11, scaled)
+    if scaled == 1:
+        assert kept > 19000
+    elif scaled == 2 ** 63:
+        assert kept == 0            # (a hash of 2 or less)
+    else:
+        assert 0 < kept < 2 * 20000 // scaled   # (1 / scaled of the windows, within a factor of two)
 
 
 @pytest.mark.parametrize("ksize", [2, 3, 11])

@@ -1,4 +1,4 @@
-"""amg_path_sketch_overlaps (amira_amd/csrc/amg_bubbles.hip) on the constructed cases of tests/path_sketch.py: sketch
+"""amg_path_sketch_overlaps (amira_amd/csrc/amg_sketch.hip) on the constructed cases of tests/path_sketch.py: sketch
 sizes and overlaps exactly as the reference's slices, sourmash's hashes and Python's sets give them
 (tests/test_path_sketch_cpu.py holds the cases and `expected` against the oracle alone) — segments that cross the seams
 of k_bs_hash's chunks at every k-mer width, the clipping of a Python slice, what a base may be, nodes listed by many
