@@ -384,20 +384,79 @@ GView make_view(amg_ctx* c) {
   return g;
 }
 
+// ------------------------------------------------------------------ row summary for the tip walk
+// Tip clipping asks little of a row: how many live edges it has and, on rows of nodes with one or two live edges in
+// all, which they are.  One pass over the directed edges answers that — no scan, no compaction, no read-back, no
+// entry array: every live edge takes a ticket of its row {count, e0, e1, -} and the holders of tickets 0 and 1 leave
+// their edge ids in the row's two slots (rows zeroed before).  Which two edges of a longer row land there depends on
+// the order of the atomics; the walk never looks (RView below).
+__global__ void k_row_tickets(const unsigned char* __restrict__ e_alive, const int* __restrict__ e_src,
+                              const signed char* __restrict__ e_sdir, long long n_edges, int4* __restrict__ rows) {
+  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_edges || !e_alive[e]) return;
+  int* r = reinterpret_cast<int*>(rows + (2ll * e_src[e] + (e_sdir[e] > 0 ? 0 : 1)));  // (the row of k_live_keys)
+  const int t = atomicAdd(r, 1);
+  if (t < 2) r[1 + t] = (int)e;
+}
+
+// The walker's view of those rows.  INVARIANT the walk keeps and this view relies on: an ENTRY is only taken from a
+// row of a node with at most two live edges in all (the walk starts at a node of degree 1 and only moves on to nodes
+// of degree 1 or 2; the closed test looks at path nodes alone), so both edges of every row it reads are in the slots.
+// Of rows with more than two live edges only the count is read (a neighbour's degree).
+struct RView {
+  const int4* rows;  // {live count, edge id of ticket 0, of ticket 1, unused}
+  const int* e_tgt;
+  const signed char* e_tdir;
+  const unsigned char* n_alive;
+  const unsigned int* n_cov;
+  const long long* n_first;
+  const int* n_comp;
+};
+
+// what the walk asks of a view: a row's live count, its first entry in list order, the target of its q-th entry
+__device__ __forceinline__ int row_count(const GView& g, long long row) { return g.lrows[row].y; }
+__device__ __forceinline__ int row_first(const GView& g, long long row, int* tgt, int* tdir) {
+  const int4 rw = g.lrows[row];
+  *tgt = rw.z;
+  *tdir = rw.w;
+  return rw.y;
+}
+__device__ __forceinline__ int row_target(const GView& g, long long row, int q) {
+  const int4 rw = g.lrows[row];
+  return q == 0 ? rw.z : g.lent[rw.x + q].x;
+}
+__device__ __forceinline__ int row_count(const RView& g, long long row) { return g.rows[row].x; }
+__device__ __forceinline__ int row_first(const RView& g, long long row, int* tgt, int* tdir) {
+  const int4 rw = g.rows[row];
+  if (rw.x == 0) return 0;
+  // list order is edge-id order: of two edges the smaller id is first
+  const int e = (rw.x == 1 || rw.y < rw.z) ? rw.y : rw.z;
+  *tgt = g.e_tgt[e];
+  *tdir = (int)g.e_tdir[e];
+  return rw.x;
+}
+__device__ __forceinline__ int row_target(const RView& g, long long row, int q) {
+  const int4 rw = g.rows[row];
+  return g.e_tgt[q == 0 ? rw.y : rw.z];
+}
+
 // get_degree (:326-329): live edge classes on both sides
-__device__ __forceinline__ int node_degree(const GView& g, int n) {
-  return g.lrows[2ll * n].y + g.lrows[2ll * n + 1].y;
+template <class View>
+__device__ __forceinline__ int node_degree(const View& g, int n) {
+  return row_count(g, 2ll * n) + row_count(g, 2ll * n + 1);
 }
 
 // get_forward_node_from_node (:722-741) / get_backward_node_from_node (:781-802):
 // forward needs EXACTLY one live forward edge, backward takes the FIRST live backward edge.
 // returns 0 = no edge, 1 = edge but cannot extend, 2 = extend
-__device__ __forceinline__ int lin_step(const GView& g, int n, bool use_forward, int* tgt, int* tdir) {
+template <class View>
+__device__ __forceinline__ int lin_step(const View& g, int n, bool use_forward, int* tgt, int* tdir) {
   const long long row = 2ll * n + (use_forward ? 0 : 1);
-  const int4 rw = g.lrows[row];
-  if (rw.y == 0 || (use_forward && rw.y != 1)) return 0;
-  *tgt = rw.z;
-  *tdir = rw.w;
+  int t = 0, d = 0;
+  const int cnt = row_first(g, row, &t, &d);
+  if (cnt == 0 || (use_forward && cnt != 1)) return 0;
+  *tgt = t;
+  *tdir = d;
   const int deg = node_degree(g, *tgt);
   return ((deg == 1 || deg == 2) && *tgt != n) ? 2 : 1;
 }
@@ -428,7 +487,9 @@ extern "C" int amg_remove_edges(amg_ctx* c, const int32_t* edge_ids, int64_t n) 
 // acc = {sum of the live nodes' coverages, number of live nodes} (k_comp_hist): the threshold is 1.5 x their mean
 // (:868-871, statistics.mean over live nodes) — the quotient of the two integers as doubles is correctly rounded,
 // == float(Fraction(sum, n)), on the device as on the host
-__global__ void k_clip_mark(GView g, long long n_nodes, int min_length, const unsigned long long* __restrict__ acc,
+// View: the live lists (GView) or the row summary (RView) — one walk, two ways to read a row
+template <class View>
+__global__ void k_clip_mark(View g, long long n_nodes, int min_length, const unsigned long long* __restrict__ acc,
                             const unsigned int* __restrict__ comp_live,
                             const unsigned char* __restrict__ protect,
                             unsigned char* __restrict__ kill) {
@@ -475,9 +536,10 @@ __global__ void k_clip_mark(GView g, long long n_nodes, int min_length, const un
     bool closed = true;
     for (int j = 0; j < len && closed; ++j)
       for (int side = 0; side < 2 && closed; ++side) {
-        const int4 rw = g.lrows[2ll * path[j] + side];
-        for (int q = 0; q < rw.y && closed; ++q) {
-          const int t = q == 0 ? rw.z : g.lent[rw.x + q].x;
+        const long long row = 2ll * path[j] + side;
+        const int cnt = row_count(g, row);  // (at most 2: a path node)
+        for (int q = 0; q < cnt && closed; ++q) {
+          const int t = row_target(g, row, q);
           bool in = false;
           for (int m = 0; m < len; ++m) in = in || (path[m] == t);
           closed = in;
@@ -636,6 +698,15 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
   // (the cleaning sweep's case; AMG_CLIP_COMPONENTS=1: A/B + test switch)
   const bool by_labels = !c->pristine || getenv("AMG_CLIP_COMPONENTS");
   if (by_labels) AMGCHK(ensure_components(c));
+  // Live lists that exist, or that k_lr_patch brings up to date (inside bubble popping, after a re-threading
+  // correction), are walked as they are.  Where there are none — the cleaning sweep's clip of a graph just built,
+  // followed by a correction that re-threads nothing and reads no lists either — the walk goes over the row summary
+  // of one pass over the edges (k_row_tickets; AMG_CLIP_LISTS=1 makes the lists as before: A/B + test switch).  The
+  // summary lives in ladj_rows while the lists are neither valid nor stale, and leaves both flags as they are:
+  // whoever needs lists next makes them from the edges, never by patching rows that are not lists.
+  const bool light = !c->ladj_valid && !c->ladj_stale && !getenv("AMG_CLIP_LISTS");
+  const long long rows = 2 * D;
+  if (light) AMGCHK(c->ladj_rows.ensure((size_t)(rows + 2) * sizeof(int4)));
   stage_begin(c, "clip");
   // live nodes per component, and the mean node coverage's two integers (:868-871), in one pass
   unsigned long long* acc = c->status.as<unsigned long long>() + ST_COV_SUM;  // (the live adjacency below uses ST_COMPACT_*)
@@ -646,8 +717,12 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
     cl.add(acc, 2 * sizeof(unsigned long long));
     cl.add(c->s0.p, (size_t)D + 8);
     if (by_labels) cl.add(c->s4.p, (size_t)(c->n_components + 2) * sizeof(unsigned int));
+    if (light) cl.add(c->ladj_rows.p, (size_t)(rows + 2) * sizeof(int4));
     AMGCHK(clear_many(c, cl));
   }
+  if (light && c->n_edges > 0)
+    hipLaunchKernelGGL(k_row_tickets, dim3(nblk(c->n_edges, 256)), dim3(256), 0, st, c->edge_alive.as<unsigned char>(),
+                       c->edge_src.as<int>(), c->edge_sdir.as<signed char>(), c->n_edges, c->ladj_rows.as<int4>());
   if (by_labels)
     hipLaunchKernelGGL(k_comp_hist, dim3(nblk(D, 256) < 256u ? nblk(D, 256) : 256u), dim3(256), 0, st, c->node_comp.as<int>(),
                        c->node_alive.as<unsigned char>(), c->node_cov.as<unsigned int>(), D, 0u,
@@ -661,10 +736,23 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
     HIPCHK(hipMemcpyAsync(c->s5.p, protect, (size_t)D, hipMemcpyHostToDevice, st));
     d_protect = c->s5.as<unsigned char>();
   }
-  AMGCHK(ensure_live_adj(c));
-  hipLaunchKernelGGL(k_clip_mark, dim3(nblk(D, 128)), dim3(128), 0, st, make_view(c), D, (int)min_length,
-                     acc, by_labels ? c->s4.as<unsigned int>() : (const unsigned int*)nullptr, d_protect,
-                     c->s0.as<unsigned char>());
+  const unsigned int* comp_live = by_labels ? c->s4.as<unsigned int>() : nullptr;
+  if (light) {
+    RView v;
+    v.rows = c->ladj_rows.as<int4>();
+    v.e_tgt = c->edge_tgt.as<int>();
+    v.e_tdir = c->edge_tdir.as<signed char>();
+    v.n_alive = c->node_alive.as<unsigned char>();
+    v.n_cov = c->node_cov.as<unsigned int>();
+    v.n_first = c->node_first.as<long long>();
+    v.n_comp = c->node_comp.as<int>();
+    hipLaunchKernelGGL(k_clip_mark<RView>, dim3(nblk(D, 128)), dim3(128), 0, st, v, D, (int)min_length, acc, comp_live,
+                       d_protect, c->s0.as<unsigned char>());
+  } else {
+    AMGCHK(ensure_live_adj(c));
+    hipLaunchKernelGGL(k_clip_mark<GView>, dim3(nblk(D, 128)), dim3(128), 0, st, make_view(c), D, (int)min_length, acc,
+                       comp_live, d_protect, c->s0.as<unsigned char>());
+  }
   int r = finish_kill(c, n_removed, removed_ids);
   stage_end(c);
   c->have_corrected = false;

@@ -224,7 +224,8 @@ struct amg_ctx {
   // live adjacency (only alive edges, targets inline) — rebuilt lazily after removals
   DevBuf ladj_off;  // int64[2 n_nodes + 1]
   DevBuf ladj;      // int2[n_live_edges]  {target node, target direction}
-  DevBuf ladj_rows; // int4[2 n_nodes]  {offset, live count, first target, first direction}
+  DevBuf ladj_rows; // int4[2 n_nodes]  {offset, live count, first target, first direction}; while the lists are neither
+                    // valid nor stale: scratch of tip clipping's row summary {live count, edge, edge, -} (amg_filter.hip)
   DevBuf ladj_pos, ladj_keys;  // scratch of the live-adjacency build (callers hold s0..s5)
   DevBuf hub_bits;             // bitmaps over the edge ids for adjacency rows beyond HUGE_ROW (huge_row_in_order)
   bool ladj_valid = false;
