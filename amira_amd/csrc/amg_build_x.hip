@@ -10,7 +10,7 @@
 //
 //   * a node slot is 16 bytes: w1 = low 63 bits of the packed tuple (+ a set bit 0), w2 =
 //     {remaining tuple bits + a set bit, where the creating window was, claim id + 1} (struct
-//     XW2).  One 16-byte (plain, L2-served) load per probe decides it; see x_upsert for when a cached view
+//     XW2).  One 16-byte (plain, L2-served) load per probe decides it; see x_upsert_one for when a cached view
 //     may be trusted.
 //   * the thread that creates a slot gives it a CLAIM id: creators of a block are counted
 //     with a block scan, one atomicAdd per block reserves the ids, the id is published in the
@@ -102,44 +102,14 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_nodes_v(
     unsigned int* __restrict__ slot_by_claim, unsigned int cap, XW2 xf, unsigned int tile0,
     unsigned long long* ctrs, unsigned int head_cap, unsigned long long fp_seed, int fp_weak) {
   // bits == 0 (K == 0 only): the key is a 94-bit fingerprint of the canonical tuple (x_fp94)
-  typedef int i4 __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) int s_tok[TILE + AMG_MAX_K + 4];
   __shared__ unsigned int s_bits[TILE_BIT_WORDS];
   __shared__ unsigned int s_wave[TILE_THREADS / 64 + 1];
   const int tid = threadIdx.x;
   const long long t0 = (long long)(blockIdx.x + tile0) * TILE;
-  // claims from the shard counters (XShard); the first tiles of the stream (the head launch and a few times as many
-  // after it) share a counter of their own and take the ids below head_cap densely
-  const XShard cshard{ctrs ? ((HEAD || (blockIdx.x + tile0) * (unsigned int)TILE < head_cap) ? (int)F_SHARDS
-                                                                                              : (int)((blockIdx.x + tile0) & (F_SHARDS - 1u)))
-                           : -1,
-                      head_cap};
+  const XShard cshard = tile_shard<HEAD>(ctrs, blockIdx.x + tile0, head_cap);
   const int flip = two_v - 1;
-  {
-    bool bad = false;
-    if (t0 + TILE <= n_tokens && (reinterpret_cast<uintptr_t>(tokens) & 15) == 0) {  // (a borrowed array may sit anywhere)
-      const i4 x = __builtin_nontemporal_load(reinterpret_cast<const i4*>(tokens + t0) + tid);
-      bad = (unsigned int)x.x >= (unsigned int)two_v || (unsigned int)x.y >= (unsigned int)two_v ||
-            (unsigned int)x.z >= (unsigned int)two_v || (unsigned int)x.w >= (unsigned int)two_v;
-      reinterpret_cast<i4*>(s_tok)[tid] = x;
-    } else {
-      for (int i = tid; i < TILE; i += TILE_THREADS) {
-        const long long t = t0 + i;
-        const int x = t < n_tokens ? tokens[t] : 0;
-        bad = bad || (unsigned int)x >= (unsigned int)two_v;
-        s_tok[i] = x;
-      }
-    }
-    if (tid < k + 3) {  // the k - 1 tokens the last windows reach into (+ padding read by the 128-bit loads)
-      const long long t = t0 + TILE + tid;
-      const int x = t < n_tokens ? tokens[t] : 0;
-      bad = bad || (unsigned int)x >= (unsigned int)two_v;
-      s_tok[TILE + tid] = x;
-    }
-    if (bad) status[ST_BADINPUT] = 2;  // a token outside [0, two_v) would alias another tuple
-    if (tid < TILE_BIT_WORDS) s_bits[tid] = bnd_bits[(t0 >> 5) + tid];
-  }
-  __syncthreads();
+  stage_tile_v(tokens, bnd_bits, n_tokens, k + 3, t0, s_tok, s_bits, two_v, status);
   const int i0 = 4 * tid;
   unsigned int id1[TILE_ITEMS];
   unsigned int last = 0, ndir = 0, valid = 0;  // per window: last of its read; direction -1; has a node
@@ -190,45 +160,36 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_nodes_v(
         status[ST_PALINDROME] = 1;  // benign race: every writer stores 1
         continue;
       }
-      idx[w] = (unsigned int)mix64(w1[w] ^ ((unsigned long long)tag[w] * 0x9E3779B97F4A7C15ull)) & mask;
+      idx[w] = hashed_slot(w1[w], tag[w], mask);
       v[w] = *reinterpret_cast<const ulonglong2*>(tab + idx[w]);  // in flight while the next window is prepared
       if (dir < 0) ndir |= 1u << w;
       valid |= 1u << w;
       if ((b >> (w + k - 1)) & 1u) last |= 1u << w;
     }
-    if constexpr (TWO)  // the slot belongs to whoever takes w1: two memory-side operations per creation instead of three
-      f_table_phase_own<1>(tab, mask, valid, w1, tag, idx, v, (unsigned int)t0 + i0, ndir, xf, first2, slot_by_claim,
-                           ctrs ? ctrs : status + ST_NODE_INSERTS, cap, probe_limit, status, 1, id1, s_wave, &made, 0u, 0u,
-                           cshard);
+    const TilePos<1, 1> pos{(unsigned int)t0 + i0, ndir};
+    unsigned long long* const ctr = ctrs ? ctrs : status + ST_NODE_INSERTS;
+    if constexpr (TWO)
+      f_table_phase_own(tab, mask, valid, w1, tag, idx, v, pos, xf, first2, slot_by_claim, ctr, cshard, cap, probe_limit,
+                        status, 1, id1, s_wave, &made);
     else
-    f_table_phase<TWO, 1, false>(tab, mask, valid, w1, tag, idx, v, (unsigned int)t0 + i0, ndir, xf, first2,
-                                 slot_by_claim, ctrs ? ctrs : status + ST_NODE_INSERTS, 0u, cap, probe_limit, status, 1,
-                                 id1, s_wave, &made, 0u, 0u, 0u, 0u, cshard);
+      f_table_phase_one(tab, mask, valid, w1, idx, v, pos, first2, slot_by_claim, ctr, cshard, cap, probe_limit, status, 1,
+                        id1, s_wave, &made);
   }
-  i4 oc;
-  unsigned int od = 0;
-  {
-    int o[TILE_ITEMS];
+  tile_i4 oc;
+  unsigned int od = 0;  // the four direction bytes
 #pragma unroll
-    for (int w = 0; w < TILE_ITEMS; ++w) {
-      o[w] = id1[w] ? (int)((id1[w] - 1u) | ((last & (1u << w)) ? AMG_LAST_FLAG : 0u) |
-                            ((made & (1u << w)) ? AMG_MADE_FLAG : 0u))
-                    : -1;
-      od |= (id1[w] ? ((ndir & (1u << w)) ? 0xffu : 1u) : 0u) << (8 * w);
-    }
-    oc = i4{o[0], o[1], o[2], o[3]};
+  for (int w = 0; w < TILE_ITEMS; ++w) {
+    oc[w] = claim_word(id1[w], last & (1u << w), made & (1u << w));
+    od |= (id1[w] ? ((ndir & (1u << w)) ? 0xffu : 1u) : 0u) << (8 * w);
   }
   const long long t = t0 + i0;
+  store_items(tok_claim, t, n_tokens, oc);
   if (t + TILE_ITEMS <= n_tokens) {
-    __builtin_nontemporal_store(oc, reinterpret_cast<i4*>(tok_claim + t));
     __builtin_nontemporal_store(od, reinterpret_cast<unsigned int*>(tok_dir + t));
   } else {
 #pragma unroll
     for (int w = 0; w < TILE_ITEMS; ++w)
-      if (t + w < n_tokens) {
-        tok_claim[t + w] = oc[w];
-        tok_dir[t + w] = (signed char)(od >> (8 * w));
-      }
+      if (t + w < n_tokens) tok_dir[t + w] = (signed char)(od >> (8 * w));
   }
 }
 
@@ -253,44 +214,14 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_nodes_m(
     signed char* __restrict__ tok_dir, unsigned long long* status, unsigned int* first2,
     unsigned int* __restrict__ slot_by_claim, unsigned int cap, XW2 xf, unsigned int tile0, unsigned int home_n,
     unsigned long long* ctrs, unsigned int head_cap) {
-  typedef int i4 __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) int s_tok[TILE + AMG_MAX_K + 4];
   __shared__ unsigned int s_bits[TILE_BIT_WORDS];
   __shared__ unsigned int s_wave[TILE_THREADS / 64 + 1];
   const int tid = threadIdx.x;
   const long long t0 = (long long)(blockIdx.x + tile0) * TILE;
-  // claims from the shard counters (XShard); the first tiles of the stream (the head launch and a few times as many
-  // after it) share a counter of their own and take the ids below head_cap densely
-  const XShard cshard{ctrs ? ((HEAD || (blockIdx.x + tile0) * (unsigned int)TILE < head_cap) ? (int)F_SHARDS
-                                                                                              : (int)((blockIdx.x + tile0) & (F_SHARDS - 1u)))
-                           : -1,
-                      head_cap};
+  const XShard cshard = tile_shard<HEAD>(ctrs, blockIdx.x + tile0, head_cap);
   const int flip = two_v - 1, V = two_v >> 1;
-  {
-    bool bad = false;
-    if (t0 + TILE <= n_tokens && (reinterpret_cast<uintptr_t>(tokens) & 15) == 0) {  // (a borrowed array may sit anywhere)
-      const i4 x = __builtin_nontemporal_load(reinterpret_cast<const i4*>(tokens + t0) + tid);
-      bad = (unsigned int)x.x >= (unsigned int)two_v || (unsigned int)x.y >= (unsigned int)two_v ||
-            (unsigned int)x.z >= (unsigned int)two_v || (unsigned int)x.w >= (unsigned int)two_v;
-      reinterpret_cast<i4*>(s_tok)[tid] = x;
-    } else {
-      for (int i = tid; i < TILE; i += TILE_THREADS) {
-        const long long t = t0 + i;
-        const int x = t < n_tokens ? tokens[t] : 0;
-        bad = bad || (unsigned int)x >= (unsigned int)two_v;
-        s_tok[i] = x;
-      }
-    }
-    if (tid < K + 3) {  // the k - 1 tokens the last windows reach into
-      const long long t = t0 + TILE + tid;
-      const int x = t < n_tokens ? tokens[t] : 0;
-      bad = bad || (unsigned int)x >= (unsigned int)two_v;
-      s_tok[TILE + tid] = x;
-    }
-    if (bad) status[ST_BADINPUT] = 2;  // a token outside [0, two_v) would alias another tuple
-    if (tid < TILE_BIT_WORDS) s_bits[tid] = bnd_bits[(t0 >> 5) + tid];
-  }
-  __syncthreads();
+  stage_tile_v(tokens, bnd_bits, n_tokens, K + 3, t0, s_tok, s_bits, two_v, status);
   unsigned int id1[TILE_ITEMS];
   unsigned int last = 0, ndir = 0, valid = 0;  // per window: last of its read; direction -1; has a node
   unsigned int made = 0;                       // per window: it created its node's key
@@ -340,25 +271,22 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_nodes_m(
       valid |= 1u << w;
       if ((b >> (K - 1)) & 1u) last |= 1u << w;
     }
+    const TilePos<1, TILE_THREADS> pos{(unsigned int)t0 + tid, ndir};
+    unsigned long long* const ctr = ctrs ? ctrs : status + ST_NODE_INSERTS;
     if constexpr (TWO)
-      f_table_phase_own<1, TILE_THREADS, AMG_BUCKET_PROBES>(tab, mask, valid, w1, tag, idx, v, (unsigned int)t0 + tid, ndir,
-                                                            xf, first2, slot_by_claim, ctrs ? ctrs : status + ST_NODE_INSERTS,
-                                                            cap, probe_limit, status, 1, id1, s_wave, &made, valid, home_n,
-                                                            cshard);
+      f_table_phase_own<1, TILE_THREADS, AMG_BUCKET_PROBES>(tab, mask, valid, w1, tag, idx, v, pos, xf, first2, slot_by_claim,
+                                                            ctr, cshard, cap, probe_limit, status, 1, id1, s_wave, &made,
+                                                            valid, home_n);
     else
-    f_table_phase<TWO, 1, false, TILE_THREADS, AMG_BUCKET_PROBES>(
-        tab, mask, valid, w1, tag, idx, v, (unsigned int)t0 + tid, ndir, xf, first2, slot_by_claim,
-        ctrs ? ctrs : status + ST_NODE_INSERTS, 0u, cap, probe_limit, status, 1, id1, s_wave, &made, valid, home_n, 0u, 0u,
-        cshard);
+      f_table_phase_one<1, TILE_THREADS, AMG_BUCKET_PROBES>(tab, mask, valid, w1, idx, v, pos, first2, slot_by_claim, ctr,
+                                                            cshard, cap, probe_limit, status, 1, id1, s_wave, &made, valid,
+                                                            home_n);
   }
 #pragma unroll
   for (int w = 0; w < TILE_ITEMS; ++w) {
     const long long t = t0 + w * TILE_THREADS + tid;
     if (t >= n_tokens) continue;
-    const int o = id1[w] ? (int)((id1[w] - 1u) | ((last & (1u << w)) ? AMG_LAST_FLAG : 0u) |
-                                 ((made & (1u << w)) ? AMG_MADE_FLAG : 0u))
-                         : -1;
-    __builtin_nontemporal_store(o, tok_claim + t);
+    __builtin_nontemporal_store(claim_word(id1[w], last & (1u << w), made & (1u << w)), tok_claim + t);
     __builtin_nontemporal_store(id1[w] ? ((ndir & (1u << w)) ? (signed char)-1 : (signed char)1) : (signed char)0, tok_dir + t);
   }
 }
@@ -428,7 +356,7 @@ __global__ void k_x_rank_setflags(const unsigned int* __restrict__ first2, long 
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const unsigned int fi = x_first_inv(first2, i);
-  if (fi == 0u) return;  // a claim id nobody took (interleaved shards, amg_build_f.hip)
+  if (fi == 0u) return;  // a claim id nobody took (the chunked shards leave holes: XShard)
   flags[(~fi) >> shift] = 1;
 }
 
@@ -608,7 +536,7 @@ __global__ void k_xc_label(const int* __restrict__ parent, const unsigned int* _
 // LONE (with HOME): `final_of_claim` carries AMG_SINGLE_BIT on the nodes of coverage 1 (k_x_cov_from_claims).  Every
 // adjacency of such a node lies next to its one window, so a class with a single end occurs once — or twice when
 // windows t - 1 and t + 1 of the single window t are the same node in the same direction (a period-2 stretch), which
-// the two neighbouring words show.  A class known to occur once needs no table: f_table_phase's lone items.
+// the two neighbouring words show.  A class known to occur once needs no table: f_table_phase_one's lone items.
 template <bool HEAD, bool HOME, bool LONE = false>  // HEAD: the short launch over the first tiles (its own symbol: per-kernel statistics keep the main launch apart)
 __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
     long long n_tokens, const int* __restrict__ tok_claim, const signed char* __restrict__ tok_dir,
@@ -617,7 +545,6 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
     unsigned int* __restrict__ slot_by_claim, unsigned int cap, XW2 xf, unsigned int tile0, unsigned int home_n,
     unsigned int lone_base, unsigned long long* ctrs, unsigned int head_cap) {
   static_assert(!LONE || HOME, "lone classes come with the home-slot layout");
-  typedef int i4 __attribute__((ext_vector_type(4)));
   // word per window: node id | single << 29 (LONE) | (direction -1) << 30 | last-of-read << 31, -1: no node
   constexpr unsigned int DIRBIT = 0x40000000u;
   constexpr unsigned int IDMASK = LONE ? AMG_SINGLE_BIT - 1u : DIRBIT - 1u;
@@ -625,12 +552,7 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
   __shared__ unsigned int s_wave[TILE_THREADS / 64 + 2];
   const int tid = threadIdx.x;
   const long long t0 = (long long)(blockIdx.x + tile0) * TILE;
-  // claims from the shard counters (XShard); the first tiles of the stream (the head launch and a few times as many
-  // after it) share a counter of their own and take the ids below head_cap densely
-  const XShard cshard{ctrs ? ((HEAD || (blockIdx.x + tile0) * (unsigned int)TILE < head_cap) ? (int)F_SHARDS
-                                                                                              : (int)((blockIdx.x + tile0) & (F_SHARDS - 1u)))
-                           : -1,
-                      head_cap};
+  const XShard cshard = tile_shard<HEAD>(ctrs, blockIdx.x + tile0, head_cap);
   const int i0 = 4 * tid;
   const long long t = t0 + i0;
   // node id of a window: -1 no node, -2 a node the merge's fused filter dropped (amg_dist.hip)
@@ -646,10 +568,10 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
   };
   int cw[TILE_ITEMS + 1];
   {
-    i4 x = {-1, -1, -1, -1};
+    tile_i4 x = {-1, -1, -1, -1};
     unsigned int d = 0;
     if (t + TILE_ITEMS <= n_tokens) {
-      x = __builtin_nontemporal_load(reinterpret_cast<const i4*>(tok_claim + t));
+      x = __builtin_nontemporal_load(reinterpret_cast<const tile_i4*>(tok_claim + t));
       d = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(tok_dir + t));
     } else {
 #pragma unroll
@@ -660,20 +582,14 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
         }
     }
     // node id per window (construct_read.py get_geneMers order), as every later stage wants it
-    i4 ids;
+    tile_i4 ids;
 #pragma unroll
     for (int w = 0; w < TILE_ITEMS; ++w) {
       const int id = node_of(x[w]);
       cw[w] = word(x[w], id, d >> (8 * w));
       ids[w] = (LONE && id >= 0) ? (int)((unsigned int)id & ~AMG_SINGLE_BIT) : id;
     }
-    if (t + TILE_ITEMS <= n_tokens) {
-      __builtin_nontemporal_store(ids, reinterpret_cast<i4*>(tok_node + t));
-    } else {
-#pragma unroll
-      for (int w = 0; w < TILE_ITEMS; ++w)
-        if (t + w < n_tokens) tok_node[t + w] = ids[w];
-    }
+    store_items(tok_node, t, n_tokens, ids);
   }
   reinterpret_cast<int4*>(s_w)[tid] = make_int4(cw[0], cw[1], cw[2], cw[3]);
   if (tid == 0) s_w[TILE] = word_at(t0 + TILE);  // the next tile's first window: right-hand neighbour of this tile's last
@@ -687,14 +603,13 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
   // adjacency (A, dA) -> (B, dB) of windows t and t + 1 of one read (create_edges :246-262); class key =
   // (smaller id, larger id, dA * dB), first-seen = (token << 3) | orientation
   unsigned long long key[TILE_ITEMS];
-  unsigned int idx[TILE_ITEMS], etag[TILE_ITEMS], id1[TILE_ITEMS];
+  unsigned int idx[TILE_ITEMS], id1[TILE_ITEMS];
   ulonglong2 v[TILE_ITEMS];
   unsigned int valid = 0, orient3 = 0, homed = 0, lone = 0;
 #pragma unroll
   for (int w = 0; w < TILE_ITEMS; ++w) {
     key[w] = 0;
     idx[w] = 0;
-    etag[w] = 0;
     const int A = HOME ? s_w[w * TILE_THREADS + tid] : cw[w], B = HOME ? s_w[w * TILE_THREADS + tid + 1] : cw[w + 1];
     if (A == -1 || ((unsigned int)A & AMG_LAST_FLAG) || B == -1) continue;
     const unsigned int a = (unsigned int)A & IDMASK, b = (unsigned int)B & IDMASK;
@@ -729,36 +644,25 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
     v[w] = *reinterpret_cast<const ulonglong2*>(etab + idx[w]);
   }
   unsigned int made = 0;
-  if constexpr (HOME)
-    f_table_phase<false, 3, false, TILE_THREADS, 1, LONE>(etab, emask, valid, key, etag, idx, v, (unsigned int)t0 + tid,
-                                                          orient3, xf, first2, slot_by_claim,
-                                                          ctrs ? ctrs : status + ST_PAIR_INSERTS, 0u, cap, probe_limit, status,
-                                                          2, id1, s_wave, &made, homed, home_n, lone, lone_base, cshard,
-                                                          ctrs ? (int)((blockIdx.x + tile0) & (F_SHARDS - 1u)) : -1);
-  else
-    f_table_phase<false, 3, false>(etab, emask, valid, key, etag, idx, v, (unsigned int)t0 + i0, orient3, xf, first2,
-                                   slot_by_claim, ctrs ? ctrs : status + ST_PAIR_INSERTS, 0u, cap, probe_limit, status, 2,
-                                   id1, s_wave, &made, 0u, 0u, 0u, 0u, cshard);
+  unsigned long long* const ctr = ctrs ? ctrs : status + ST_PAIR_INSERTS;
   if constexpr (HOME) {
+    // (the lone classes of a first tile take their ids from the tile's own shard: f_table_phase_one)
+    f_table_phase_one<3, TILE_THREADS, 1, LONE>(etab, emask, valid, key, idx, v, {(unsigned int)t0 + tid, orient3}, first2,
+                                                slot_by_claim, ctr, cshard, cap, probe_limit, status, 2, id1, s_wave, &made,
+                                                homed, home_n, lone, lone_base,
+                                                tile_shard<false>(ctrs, blockIdx.x + tile0, 0u));
 #pragma unroll
     for (int w = 0; w < TILE_ITEMS; ++w) {
       const long long tw = t0 + w * TILE_THREADS + tid;
-      if (tw < n_tokens)
-        __builtin_nontemporal_store(id1[w] ? (int)((id1[w] - 1u) | ((made & (1u << w)) ? AMG_MADE_FLAG : 0u)) : -1,
-                                    tok_pair + tw);
+      if (tw < n_tokens) __builtin_nontemporal_store(claim_word(id1[w], false, made & (1u << w)), tok_pair + tw);
     }
   } else {
-    i4 op;
+    f_table_phase_one<3, 1>(etab, emask, valid, key, idx, v, {(unsigned int)t0 + i0, orient3}, first2, slot_by_claim, ctr,
+                            cshard, cap, probe_limit, status, 2, id1, s_wave, &made);
+    tile_i4 op;
 #pragma unroll
-    for (int w = 0; w < TILE_ITEMS; ++w)
-      op[w] = id1[w] ? (int)((id1[w] - 1u) | ((made & (1u << w)) ? AMG_MADE_FLAG : 0u)) : -1;
-    if (t + TILE_ITEMS <= n_tokens) {
-      __builtin_nontemporal_store(op, reinterpret_cast<i4*>(tok_pair + t));
-    } else {
-#pragma unroll
-      for (int w = 0; w < TILE_ITEMS; ++w)
-        if (t + w < n_tokens) tok_pair[t + w] = op[w];
-    }
+    for (int w = 0; w < TILE_ITEMS; ++w) op[w] = claim_word(id1[w], false, made & (1u << w));
+    store_items(tok_pair, t, n_tokens, op);
   }
 }
 

@@ -30,7 +30,6 @@
 #include <dlfcn.h>
 
 #include "amg_dist.h"
-#include "amg_x.h"
 
 #define NEED_CTX(c)                                              \
   do {                                                           \

@@ -87,6 +87,52 @@ __device__ __forceinline__ void stage_tile(const int* __restrict__ tokens,
   __syncthreads();
 }
 
+// The same for the kernels that cut their windows with 128-bit LDS reads (k_nodes_v, k_nodes_m): a full tile of an
+// array on a 16-byte boundary arrives in one 128-bit non-temporal load per thread (a borrowed array may sit anywhere:
+// the scalar route), then the `halo` tokens behind the tile — the k - 1 the last windows reach into + the padding the
+// 128-bit reads touch, halo <= TILE_THREADS.
+typedef int tile_i4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void stage_tile_v(const int* __restrict__ tokens, const unsigned int* __restrict__ bnd_bits,
+                                             long long n_tokens, int halo, long long t0, int* s_tok,
+                                             unsigned int* s_bits, int two_v, unsigned long long* status) {
+  const int tid = threadIdx.x;
+  bool bad = false;
+  if (t0 + TILE <= n_tokens && (reinterpret_cast<uintptr_t>(tokens) & 15) == 0) {
+    const tile_i4 x = __builtin_nontemporal_load(reinterpret_cast<const tile_i4*>(tokens + t0) + tid);
+    bad = (unsigned int)x.x >= (unsigned int)two_v || (unsigned int)x.y >= (unsigned int)two_v ||
+          (unsigned int)x.z >= (unsigned int)two_v || (unsigned int)x.w >= (unsigned int)two_v;
+    reinterpret_cast<tile_i4*>(s_tok)[tid] = x;
+  } else {
+    for (int i = tid; i < TILE; i += TILE_THREADS) {
+      const long long t = t0 + i;
+      const int x = t < n_tokens ? tokens[t] : 0;
+      bad = bad || (unsigned int)x >= (unsigned int)two_v;
+      s_tok[i] = x;
+    }
+  }
+  if (tid < halo) {
+    const long long t = t0 + TILE + tid;
+    const int x = t < n_tokens ? tokens[t] : 0;
+    bad = bad || (unsigned int)x >= (unsigned int)two_v;
+    s_tok[TILE + tid] = x;
+  }
+  if (bad) status[ST_BADINPUT] = 2;  // a token outside [0, two_v) would alias another tuple
+  if (tid < TILE_BIT_WORDS) s_bits[tid] = bnd_bits[(t0 >> 5) + tid];
+  __syncthreads();
+}
+
+// the four consecutive results of a thread, out[t .. t + 3]: one 16-byte non-temporal store, or item by item where
+// the array ends (n: its length; t a multiple of 4, the array on a 16-byte boundary)
+__device__ __forceinline__ void store_items(int* __restrict__ out, long long t, long long n, tile_i4 x) {
+  if (t + TILE_ITEMS <= n) {
+    __builtin_nontemporal_store(x, reinterpret_cast<tile_i4*>(out + t));
+  } else {
+#pragma unroll
+    for (int w = 0; w < TILE_ITEMS; ++w)
+      if (t + w < n) out[t + w] = x[w];
+  }
+}
+
 // bits [pos, pos + n) of the tile's bitmap slice, n <= 32
 __device__ __forceinline__ unsigned int tile_bits(const unsigned int* s_bits, int pos, int n) {
   const unsigned long long w =

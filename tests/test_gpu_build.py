@@ -299,3 +299,120 @@ def test_edge_classes_of_single_nodes(lone, shards, monkeypatch):
             assert np.array_equal(tok_node, want["tok_node"]) and np.array_equal(tok_dir, want["tok_dir"])
     finally:
         eng.close()
+
+
+SEAMS = (1024, 2048)                         # tile seams of a stream of up to three 1024-token tiles
+SEAM_SIZES = (1024, 2049, 3074, 3075)        # T % 4 = 0, 1, 2, 3: one full tile; an inner tile, a last tile, both seams
+_seam_cases = {}                             # (T, layout, k, V) -> (tokens, offsets, oracle's graph): made once, never changed
+
+
+def _seam_case(T, layout, k, V):
+    """A stream of exactly T tokens in reads of 1 to 14 genes over a few genes of the vocabulary, with, around every
+    tile seam s it reaches: layout "ends" — a read of k + 2 genes that ends at token s - 1, one-gene reads that end at s
+    and s + 1, a read of k + 2 genes that starts there; layout "straddle" — one read with k + 1 genes on either side
+    of s.  Returns None when the layout plants nothing in T tokens."""
+    import token_oracle
+    key = (T, layout, k, V)
+    if key in _seam_cases:
+        return _seam_cases[key]
+    planted = []
+    for s in SEAMS:
+        if layout == "ends":
+            planted += [(s - 1 - (k + 2), s - 1), (s - 1, s), (s, s + 1), (s + 1, s + 1 + k + 2)]
+        elif s + k <= T:
+            planted.append((s - k - 1, s + k + 1))
+    planted = [(a, min(b, T)) for a, b in planted if a < T]
+    if not planted:
+        _seam_cases[key] = None
+        return None
+    rng = np.random.default_rng(1000 * k + T + (layout == "ends"))
+    cuts, at = [0], 0
+    for a, b in planted + [(T, T)]:
+        while at < a:                        # reads of 1 to 14 genes up to the next planted read
+            at = min(a, at + int(rng.integers(1, 15)))
+            cuts.append(at)
+        if b > a:
+            cuts.append(b)
+            at = b
+    offs = np.asarray(cuts, np.int64)
+    assert offs[-1] == T and np.all(np.diff(offs) > 0)
+    # few genes, both strands of each, so that gene-mers repeat: 10^3, 4^5, 4^7, 2^11 possible windows
+    genes = rng.choice(V, {3: 5, 5: 2, 7: 2}.get(k, 1), replace=False)
+    toks = rng.choice(np.concatenate([V + genes, V - 1 - genes]), T).astype(np.int32)
+    # the arrangements are there
+    ends = set(offs.tolist())
+    if layout == "ends":
+        for e in (1023, 1024, 1025, 2047, 2048, 2049):
+            assert e > T or e in ends, e
+        assert all(np.any((offs[1:] == s - 1) & (np.diff(offs) >= k)) for s in SEAMS if s - 1 <= T)
+    else:
+        assert all(np.any((offs[:-1] <= s - k) & (offs[1:] >= s + k)) for s in SEAMS if s + k <= T)
+    _seam_cases[key] = (toks, offs, token_oracle.build(toks, offs, k, 2 * V))
+    return _seam_cases[key]
+
+
+SEAM_ARMS = [  # (environment, [(k, V, exact_keys as amg_counts reports it)])
+    ({"AMG_NODE_BUCKETS": b}, [kv]) for b in ("0", "1")
+    for kv in ((3, 12, 1),       # one key word, 16-bit packing
+               (5, 30000, 1),    # two key words (80 bits)
+               (7, 32, 1),       # general packing (6 bits per gene), one key word
+               (11, 400, 2))     # 110 bits: fingerprint keys, the kernel with k at run time
+] + [({"AMG_X_GENERIC_K": "1"}, [(3, 12, 1), (5, 30000, 1)]),   # exact keys through the kernel with k at run time
+     ({"AMG_EDGE_HOME": "0"}, [(3, 12, 1), (5, 30000, 1)]),     # four consecutive adjacencies per thread
+     ({"AMG_CLAIM_SHARDS": "1", "AMG_X_HEAD_TILES": "1"}, [(3, 12, 1), (5, 30000, 1)])]  # a head tile, a dense tile, a shard's
+
+
+@pytest.mark.parametrize("env,shapes", SEAM_ARMS, ids=lambda a: "-".join(f"{k[4:]}={v}" for k, v in a.items())
+                         if isinstance(a, dict) else "k" + "+".join(str(s[0]) for s in a))
+def test_tile_seams_and_staging_routes(env, shapes, monkeypatch):
+    """What the node and edge kernels do around a tile: reads that end one token before, at and one token after a tile
+    seam, reads that lie across a seam with more than k genes on either side, and streams whose length is 0, 1, 2 and
+    3 modulo the four results a thread stores at once — for one- and two-word keys in both packings, fingerprint keys,
+    k at compile and at run time, with and without minimiser buckets, home slots and shard counters.  At k = 3 and 5
+    every stream is also built from a BORROWED device array that starts 4, 8 or 12 bytes after a 16-byte boundary (the
+    tile then arrives by the scalar route instead of one 128-bit load per thread).  Everything against the sequential C
+    oracle, exactly."""
+    import torch
+    from amira_amd import Engine
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    eng = Engine(0)
+
+    def check(want, k, exact, what):
+        c = eng.counts()
+        assert c["exact_keys"] == exact and c["n_windows"] == want["n_windows"], what
+        nodes, edges = eng.nodes(), eng.edges()
+        tok_node, tok_dir = eng.read_nodes()
+        assert np.array_equal(nodes["tokens"], want["tokens"]), what
+        assert np.array_equal(nodes["coverage"], want["coverage"]), what
+        assert np.array_equal(nodes["first_dir"], want["first_dir"]), what
+        for a, b in (("src", "src"), ("tgt", "tgt"), ("sdir", "sdir"), ("tdir", "tdir"), ("coverage", "ecov")):
+            assert np.array_equal(edges[a], want[b]), (what, a)
+        assert np.array_equal(tok_node, want["tok_node"]) and np.array_equal(tok_dir, want["tok_dir"]), what
+
+    try:
+        built = 0
+        for k, V, exact in shapes:
+            for T in SEAM_SIZES:
+                for layout in ("ends", "straddle"):
+                    case = _seam_case(T, layout, k, V)
+                    if case is None:         # (no seam inside one tile to lie across)
+                        continue
+                    toks, offs, want = case
+                    eng.set_reads(toks, offs, 2 * V)
+                    eng.build(k)
+                    check(want, k, exact, (k, T, layout, "host arrays"))
+                    built += 1
+                    if k not in (3, 5):
+                        continue
+                    pad = 1 + built % 3      # int32 elements in front: the array starts 4 * pad bytes after a boundary
+                    buf = torch.zeros(pad + T, dtype=torch.int32, device="cuda")
+                    buf[pad:] = torch.from_numpy(toks).cuda()
+                    d_offs = torch.from_numpy(offs).cuda()
+                    assert (buf.data_ptr() + 4 * pad) % 16 == 4 * pad and d_offs.data_ptr() % 16 == 0
+                    eng.set_reads_device(buf.data_ptr() + 4 * pad, d_offs.data_ptr(), len(offs) - 1, 2 * V, borrow=True)
+                    eng.build(k)
+                    check(want, k, exact, (k, T, layout, "borrowed, %d bytes off" % (4 * pad)))
+        assert built == len(shapes) * 7      # ends: every size; straddle: the three sizes with a seam inside
+    finally:
+        eng.close()
