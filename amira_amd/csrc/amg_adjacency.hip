@@ -1,16 +1,17 @@
 // amg_adjacency.hip — the two views of a built graph that are made on first use, whichever key scheme built it: the full
 // forward / backward edge lists of every node (ensure_adjacency) and the component ids (ensure_components).  amg_finalize
-// asks for both; a cleaning sweep asks for what it needs.  (The LIVE adjacency the walkers read is amg_filter.hip's.)
-#include "amg_device.h"
+// asks for both; a cleaning sweep asks for what it needs.  The lists of the LIVE edges, which the walkers read, are
+// amg_live_rows.hip's; both units put a row's ids in order with amg_rows.h.
+#include "amg_rows.h"
 
 // ------------------------------------------------------------------ full adjacency lists
-// adjacency rows: row = 2 * src + (sdir == +1 ? 0 : 1); edge ids ascending inside a row
+// adjacency rows: adj_row_of; edge ids ascending inside a row
 __global__ void k_adj_keys(const int* __restrict__ e_src, const signed char* __restrict__ e_sdir,
                            long long n_edges, unsigned int* __restrict__ keys,
                            unsigned int* __restrict__ vals) {
   long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_edges) return;
-  keys[e] = 2u * (unsigned int)e_src[e] + (e_sdir[e] > 0 ? 0u : 1u);
+  keys[e] = adj_row_of(e_src[e], e_sdir[e]);
   vals[e] = (unsigned int)e;
 }
 
@@ -30,24 +31,19 @@ __global__ void k_row_offsets(const unsigned int* __restrict__ keys, long long n
 //   k_adjc_ticket  every edge draws a ticket of its row (rows zeroed before): row sizes and a place inside the row
 //   (scan)         row sizes -> CSR offsets
 //   k_adjc_fill    every edge drops its id at offset + ticket (any order within the row)
-//   k_adjc_rows    a thread per row puts the row's ids in ascending order (= list order: edge ids follow insertion
-//                  order; rows of 3 .. 64 by the wave); rows longer than a wave are left to k_adjc_long, a workgroup per long row (hub nodes)
-__device__ __forceinline__ unsigned int adj_row_of(const int* __restrict__ e_src, const signed char* __restrict__ e_sdir,
-                                                   long long e) {
-  return 2u * (unsigned int)e_src[e] + (e_sdir[e] > 0 ? 0u : 1u);
-}
-
+//   k_adjc_rows    a thread per row puts the row's ids in ascending order (short_rows_in_order, amg_rows.h); rows longer
+//                  than a wave are left to k_adjc_long (long_rows_in_order: hub nodes)
 __global__ void k_adjc_ticket(const int* __restrict__ e_src, const signed char* __restrict__ e_sdir, long long n_edges,
                               unsigned int* __restrict__ cnt, unsigned int* __restrict__ tick) {
   long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n_edges) tick[e] = atomicAdd(&cnt[adj_row_of(e_src, e_sdir, e)], 1u);
+  if (e < n_edges) tick[e] = atomicAdd(&cnt[adj_row_of(e_src[e], e_sdir[e])], 1u);
 }
 
 __global__ void k_adjc_fill(const int* __restrict__ e_src, const signed char* __restrict__ e_sdir, long long n_edges,
                             const long long* __restrict__ off, const unsigned int* __restrict__ tick,
                             unsigned int* __restrict__ tmp) {
   long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n_edges) tmp[off[adj_row_of(e_src, e_sdir, e)] + tick[e]] = (unsigned int)e;
+  if (e < n_edges) tmp[off[adj_row_of(e_src[e], e_sdir[e])] + tick[e]] = (unsigned int)e;
 }
 
 __global__ __launch_bounds__(256) void k_adjc_rows(const long long* __restrict__ off, long long n_rows,
@@ -60,52 +56,18 @@ __global__ __launch_bounds__(256) void k_adjc_rows(const long long* __restrict__
     o = off[r];
     cnt = (int)(off[r + 1] - o);
   }
-  bool mine = cnt > 2;
-  if (cnt == 1) {
-    adj_edge[o] = (int)tmp[o];
-  } else if (cnt == 2) {
-    const unsigned int a = tmp[o], b = tmp[o + 1];
-    adj_edge[o] = (int)(a < b ? a : b);
-    adj_edge[o + 1] = (int)(a < b ? b : a);
-  } else if (cnt > WAVE_ROW_MAX) {
-    long_rows[atomicAdd(n_long, 1ull)] = (unsigned int)r;
-    mine = false;
-  }
-  // rows of 3 .. 64 ids: by the wave, one row at a time (wave_rows_in_order, amg_device.h)
-  wave_rows_in_order(mine, 0u, o, cnt, tmp,
-                     [&](unsigned int, long long ro, int, int rank, unsigned int x) { adj_edge[ro + rank] = (int)x; });
+  short_rows_in_order(cnt > 0, (unsigned int)r, o, cnt, tmp, long_rows, n_long,
+                      [&](unsigned int, long long ro, int, long long rank, unsigned int x) { adj_edge[ro + rank] = (int)x; });
 }
 
-// a workgroup per long row: every element finds its rank among the row's (distinct) edge ids; rows beyond HUGE_ROW are
-// left to the first HUB_BLOCKS workgroups, which put them in order through a bitmap (huge_row_in_order, amg_device.h)
-#define HUB_BLOCKS 8
 __global__ __launch_bounds__(256) void k_adjc_long(const unsigned int* __restrict__ long_rows,
                                                    const unsigned long long* __restrict__ n_long,
                                                    const long long* __restrict__ off, const unsigned int* __restrict__ tmp,
                                                    int* __restrict__ adj_edge, unsigned int* hub_bits, long long hub_words) {
   __shared__ unsigned int s_wave[4];
-  const unsigned long long n = *n_long;
-  for (unsigned long long q = blockIdx.x; q < n; q += gridDim.x) {
-    const unsigned int r = long_rows[q];
-    const long long o = off[r];
-    const int cnt = (int)(off[r + 1] - o);
-    if (cnt > HUGE_ROW) continue;
-    for (int j = threadIdx.x; j < cnt; j += 256) {
-      const unsigned int x = tmp[o + j];
-      int rank = 0;
-      for (int i = 0; i < cnt; ++i) rank += tmp[o + i] < x ? 1 : 0;
-      adj_edge[o + rank] = (int)x;
-    }
-  }
-  if (blockIdx.x >= HUB_BLOCKS) return;
-  for (unsigned long long q = blockIdx.x; q < n; q += HUB_BLOCKS) {  // (block-uniform: every thread takes the same rows)
-    const unsigned int r = long_rows[q];
-    const long long o = off[r];
-    const long long cnt = off[r + 1] - o;
-    if (cnt <= HUGE_ROW) continue;
-    huge_row_in_order(tmp + o, cnt, hub_bits + (long long)blockIdx.x * hub_words, hub_words, s_wave,
-                      [&](long long rank, unsigned int id) { adj_edge[o + rank] = (int)id; });
-  }
+  long_rows_in_order(
+      long_rows, *n_long, [&](unsigned int r) { return RowSpan{off[r], (int)(off[r + 1] - off[r])}; }, tmp, hub_bits,
+      hub_words, s_wave, [&](unsigned int, long long ro, int, long long rank, unsigned int x) { adj_edge[ro + rank] = (int)x; });
 }
 
 // ------------------------------------------------------------------ components

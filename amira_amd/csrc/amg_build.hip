@@ -109,8 +109,7 @@ int bs_finish_from_pairs(amg_ctx* c) {
   }
   c->n_edges = total;
   stage_end(c);
-  c->ladj_valid = false;
-  c->ladj_stale = false;
+  live_lists_after_build(c);
   c->pristine = !c->comp_from_claims;  // (a filtered build's labels are those of the graph BEFORE its filter)
   c->edge_own_deaths = false;
   c->comp_valid = false;

@@ -156,64 +156,7 @@ __device__ __forceinline__ unsigned int block_exscan_256(unsigned int v, unsigne
   return block_exscan<4>(v, total, s_wave);
 }
 
-// ------------------------------------------------------------------ a hub row's ids in ascending order
-// Rows of an adjacency list are put in order by rank (every id counts the smaller ids of its row): fine for the rows of
-// a gene-mer graph, quadratic in the row.  A row longer than HUGE_ROW goes through a bitmap over the id space instead —
-// clear, set one bit per id, prefix-count the words, read the ids off in order: O(ids / 32 + row) for a workgroup,
-// whatever the row's length (a hub with a million neighbours would otherwise hold one workgroup for an hour).
-// bits: this workgroup's scratch of `words` words; emit(rank, id).  All 256 threads of the workgroup call it.
-// Rows of 3 .. 64 edge ids in ascending order by the WAVE, one row at a time: every lane that holds such a row (`mine`)
-// is served in turn — lane j takes the row's j-th id, its rank is the number of smaller ids (one shuffle per id of the
-// row), emit(row's tag, row's offset, row's length, rank, id) places it.  A thread per row with an insertion sort in a private array was the tail
-// of the list kernels: a row of thirty ids is ~500 dependent scratch accesses of ONE lane (0.9 ms for the genome rows
-// of a graph that carries the residual error nodes of eight read sets), here ~30 shuffles of a wave.
-// Every lane of the wave must call (no early returns before).
-#define WAVE_ROW_MAX 64
-template <class Emit>
-__device__ __forceinline__ void wave_rows_in_order(bool mine, unsigned int tag, long long off, int cnt,
-                                                   const unsigned int* __restrict__ ids, Emit emit) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(mine);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    todo &= todo - 1ull;
-    const long long o = __shfl(off, leader, 64);
-    const int n = __shfl(cnt, leader, 64);
-    const unsigned int tg = __shfl(tag, leader, 64);
-    const unsigned int x = lane < n ? ids[o + lane] : 0xffffffffu;
-    int rank = 0;
-    for (int q = 0; q < n; ++q) rank += __shfl(x, q, 64) < x ? 1 : 0;
-    if (lane < n) emit(tg, o, n, rank, x);
-  }
-}
-
-#define HUGE_ROW 1024
-template <class Emit>
-__device__ __forceinline__ void huge_row_in_order(const unsigned int* __restrict__ ids, long long cnt, unsigned int* bits,
-                                                  long long words, unsigned int* s_wave /*[4]*/, Emit emit) {
-  for (long long w = threadIdx.x; w < words; w += 256) bits[w] = 0u;
-  __threadfence();
-  __syncthreads();
-  for (long long j = threadIdx.x; j < cnt; j += 256) atomicOr(&bits[ids[j] >> 5], 1u << (ids[j] & 31u));
-  __threadfence();
-  __syncthreads();
-  const long long per = (words + 255) / 256;
-  const long long w0 = (long long)threadIdx.x * per, w1 = w0 + per < words ? w0 + per : words;
-  unsigned int mine = 0;
-  for (long long w = w0; w < w1; ++w)
-    mine += (unsigned int)__popc(__hip_atomic_load(bits + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  unsigned int total;
-  unsigned int rank = block_exscan_256(mine, &total, s_wave);
-  for (long long w = w0; w < w1; ++w) {
-    unsigned int v = __hip_atomic_load(bits + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (v) {
-      const int b = __ffs((int)v) - 1;
-      v &= v - 1u;
-      emit((long long)rank++, (unsigned int)(w * 32 + b));
-    }
-  }
-  __syncthreads();
-}
+// (adjacency rows — row keys, ids in ascending order, the walkers' row accessors — are amg_rows.h)
 
 // ------------------------------------------------------------------ range clears (k_clear_many; the scans' side clears)
 struct ClearArgs {
@@ -266,5 +209,3 @@ __device__ __forceinline__ int uf_find(int* parent, int x) {
   }
   return x;
 }
-
-

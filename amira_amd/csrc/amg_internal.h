@@ -156,6 +156,15 @@ struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until th
 struct SketchState;  // amg_sketch.hip: the buffers of amg_path_sketch_overlaps
 struct PopState;     // amg_pop.hip: the buffers of amg_pop_rewrite
 
+// What ladj / ladj_rows hold (transitions: live_lists_after_*, ensure_live_adj; amg_live_rows.hip).
+// While the state is Absent, and only then, ladj_rows is free to hold tip clipping's row summary {live count, edge, edge,
+// -} (row_summary); making the summary leaves the state Absent.
+enum class LiveLists {
+  Absent,       // no lists of the graph as it is: the next walker makes them from the live edges
+  Current,      // the lists of the graph as it is
+  BehindNodes,  // the lists of the graph before some NODES died (no edge died with both ends alive): k_lr_patch brings them up to date
+};
+
 struct amg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -221,15 +230,12 @@ struct amg_ctx {
   // adjacency CSR, row 2n = forward list of node n, 2n+1 = backward list
   DevBuf adj_off;   // int64[2 n_nodes + 1]
   DevBuf adj_edge;  // int32[n_edges]
-  // live adjacency (only alive edges, targets inline) — rebuilt lazily after removals
-  DevBuf ladj_off;  // int64[2 n_nodes + 1]
+  // live adjacency (only alive edges, targets inline) — made on first use after removals (amg_live_rows.hip)
   DevBuf ladj;      // int2[n_live_edges]  {target node, target direction}
-  DevBuf ladj_rows; // int4[2 n_nodes]  {offset, live count, first target, first direction}; while the lists are neither
-                    // valid nor stale: scratch of tip clipping's row summary {live count, edge, edge, -} (amg_filter.hip)
+  DevBuf ladj_rows; // int4[2 n_nodes]  {offset, live count, first target, first direction}
   DevBuf ladj_pos, ladj_keys;  // scratch of the live-adjacency build (callers hold s0..s5)
-  DevBuf hub_bits;             // bitmaps over the edge ids for adjacency rows beyond HUGE_ROW (huge_row_in_order)
-  bool ladj_valid = false;
-  bool ladj_stale = false;  // the live lists are those of the graph before some NODES died (ensure_live_adj patches them)
+  DevBuf hub_bits;             // bitmaps over the edge ids for adjacency rows beyond HUGE_ROW (huge_row_in_order, amg_rows.h)
+  LiveLists live_lists = LiveLists::Absent;
   bool comp_valid = false, adj_valid = false;  // component ids / full edge lists of the built graph are made on demand
   bool pristine = false;  // nothing has been removed since the build, and its component labels are those of the graph as it is
   // reads
@@ -408,7 +414,7 @@ void stage_begin(amg_ctx* c, const char* name);
 void stage_end(amg_ctx* c);
 void stages_reset(amg_ctx* c);
 
-// ------------------------------------------------------------------ walkers' view of the live graph (amg_filter.hip)
+// ------------------------------------------------------------------ walkers' view of the live graph (amg_live_rows.hip)
 struct GView {
   // live adjacency: row 2n = forward list of node n, row 2n+1 = backward list, only ALIVE
   // edges, in list order, with the target inline (.x = target node, .y = target direction)
@@ -424,6 +430,10 @@ struct GView {
 };
 int ensure_live_adj(amg_ctx* c);  // the live lists below exist and are up to date
 GView make_view(amg_ctx* c);
+// what happened to the graph, as far as its live lists (and pristine, edge_own_deaths, match_valid) are concerned
+void live_lists_after_node_deaths(amg_ctx* c);  // nodes died, and every edge that died has a dead end
+void live_lists_after_edge_deaths(amg_ctx* c);  // an edge died with both its ends alive
+void live_lists_after_build(amg_ctx* c);        // a new graph
 void bubbles_release(amg_ctx* c);  // amg_bubbles.hip
 void sketch_release(amg_ctx* c);   // amg_sketch.hip
 void pop_release(amg_ctx* c);  // amg_pop.hip

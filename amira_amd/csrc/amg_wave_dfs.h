@@ -29,7 +29,7 @@ __device__ __forceinline__ void wave_dfs(const GView& g, int start, int start_di
   bool entering = true;
   // A row record carries the row's first entry {z, w} next to {offset, live count}: the row just entered needs no
   // load from lent for it.  This cannot change what is found: every writer of a row record stores lent[offset] and
-  // {z, w} from the same values (k_lr_fill, k_lr_finish, k_lr_long, k_lr_patch in amg_filter.hip).
+  // {z, w} from the same values (k_lr_fill, k_lr_finish, k_lr_long, k_lr_patch in amg_live_rows.hip).
   int2 first_ent = make_int2(-1, 0);
   while (depth >= 0) {
     const int d = __builtin_amdgcn_readfirstlane(depth);

@@ -1,4 +1,4 @@
-"""Tip clipping on the one-pass row summary (k_row_tickets / RView, amg_filter.hip) against the CPU oracle, and against
+"""Tip clipping on the one-pass row summary (k_row_tickets, amg_live_rows.hip; RView, amg_rows.h) against the CPU oracle, and against
 the walk over the live lists (AMG_CLIP_LISTS=1), which must agree with it to the last id.
 
 A case is a read set, a gene-mer size and a list of steps applied to the engine and to the oracle after the build:

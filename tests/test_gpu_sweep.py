@@ -372,7 +372,7 @@ def test_positions_32_bit_at_the_boundary(seed, N, L, V, k, err):
 def test_sweep_with_a_hub_of_fifteen_hundred_neighbours(eng):
     """one gene-mer followed by 1 500 different ones: the hub's rows of the adjacency lists (all edges, amg_finalize;
     live edges, tip clipping and the correction) are longer than HUGE_ROW and are put in order through a bitmap over
-    the edge ids instead of by rank (huge_row_in_order, amg_device.h); a second, smaller hub takes the rank route"""
+    the edge ids instead of by rank (huge_row_in_order, amg_rows.h); a second, smaller hub takes the rank route"""
     from amira_amd import synth
     reads = {}
     for i in range(1500):
