@@ -3,6 +3,7 @@
 // back) with the stage functions that work on it.
 //   amg_correct.hip         classify, shape, pack, and amg_correct_reads itself (the pipeline is described there)
 //   amg_correct_gapped.hip  re-threading of the reads with None runs      (stage correct_gapped)
+//   amg_gap_memo.hip        the path memo's search, a lane per question   (stage correct_gapped)
 //   amg_correct_nw.hip      position carry-over of the re-threaded reads  (stage correct_positions)
 //   amg_corrected.hip       the corrected set at the boundary (it gathers positions through CorrArgs' pools)
 #pragma once
@@ -201,6 +202,7 @@ struct PackArgs {
 // calls on one engine); NAME=1 switches the named thing off.
 struct CorrSwitches {
   bool gap_memo;            // AMG_NO_GAP_MEMO: every read searches its own paths
+  bool gap_dfs_wave;        // AMG_GAP_DFS_WAVE=1 (switches ON): the memo's questions a wave each (k_gap_dfs) at every k
   bool fast_gapped;         // AMG_NO_FAST_GAPPED: every gapped read through the general one-thread kernel
   bool lean_gapped;         // AMG_NO_LEAN_GAPPED: every gapped read through the wave-per-read kernel
   int fast_nw;              // AMG_NO_FAST_NW: every carry-over through the general kernel
@@ -273,6 +275,12 @@ int corr_nw_sizes(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, cons
 int corr_grow_pos_pools(amg_ctx* c, const CorrCounts& n);
 int corr_positions(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n,
                    unsigned char* route = nullptr);  // route: NwArgs::route (amg_nw_probe only)
+
+// the path memo's search a lane per question (amg_gap_memo.hip): for the k whose search fits its stack, else k_gap_dfs
+bool gap_dfs_lanes_fits(int k);
+void gap_dfs_lanes_launch(amg_ctx* c, const int* qlist, long long n_queries, const unsigned long long* qtab,
+                          unsigned long long* pool_used, unsigned long long pool_cap, int* qpool, int4* qres,
+                          int* qgene);
 
 // ---- route report (amg_correct_routes.hip), only with CorrSwitches::routes: small tally kernels behind the steps
 int routes_begin(amg_ctx* c);

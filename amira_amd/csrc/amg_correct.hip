@@ -123,6 +123,7 @@ static CorrSwitches read_switches() {
   };
   CorrSwitches sw;
   sw.gap_memo = !is_one("AMG_NO_GAP_MEMO");
+  sw.gap_dfs_wave = is_one("AMG_GAP_DFS_WAVE");
   sw.fast_gapped = !is_one("AMG_NO_FAST_GAPPED");
   sw.lean_gapped = !is_one("AMG_NO_LEAN_GAPPED");
   sw.fast_nw = !is_one("AMG_NO_FAST_NW");

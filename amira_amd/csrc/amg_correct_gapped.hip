@@ -3,14 +3,16 @@
 // and the three gapped kernels, with the host function that runs them.  (Pipeline: amg_correct.hip.)
 //   k_corr_classify                      (amg_correct.hip's classify step: see below why it is compiled here)
 //   dfs_paths, k_corr_gapped             the general kernel: a thread per read, its search stack in private arrays
-//   dfs_paths_wave                       the re-threading's visitor on the wave-cooperative search (amg_wave_dfs.h)
-//   k_gap_queries, k_gap_dfs             the path memo: every distinct question of the None runs answered once
+//   k_gap_queries, k_gap_dfs             the path memo: every distinct question of the None runs answered once (a wave
+//                                        per question; a lane per question, k_gap_dfs_lanes, is amg_gap_memo.hip's)
 //   k_corr_gapped_lean                   sixteen lanes per read: the reads whose every question has one answer
 //   gf_* steps, gapped_fast_read, k_corr_gapped_fast   a wave per read, staged in LDS (GfLds)
 //   gap_memo, corr_gapped                the host side
 // (The None runs of a live-window mask: gap_run_ends / gap_run_terminals in amg_correct.h.)
+// (dfs_paths_wave — the re-threading's visitor on the wave-cooperative search —, oriented_tok and the memo's question
+// key: amg_gap_search.h, shared with amg_gap_memo.hip.)
 #include "amg_correct.h"
-#include "amg_wave_dfs.h"
+#include "amg_gap_search.h"
 
 // ---- classification.  The kernel belongs to amg_correct.hip's classify step and is launched from here only because
 // of what the compiler does with it: the device library's 64-bit count-leading-zeros helper is optimised differently
@@ -217,12 +219,6 @@ __device__ void dfs_paths(const GView& g, int s, int sdir, int e, int distance, 
   }
 }
 
-// last gene of node n taken in direction d (get_gene_mer_genes / get_reverse_gene_mer_genes)
-__device__ __forceinline__ int oriented_tok(const GView& g, int n, int d, int j) {
-  const int* nt = g.n_tok + (long long)n * g.k;
-  return d == 1 ? nt[j] : g.flip - nt[g.k - 1 - j];
-}
-
 struct GapIter {
   long long t0;
   const int* tok_node;
@@ -401,57 +397,13 @@ __global__ __launch_bounds__(64) void k_corr_gapped(GapArgs A) {
 // general one-thread-per-read kernel above; results are identical by construction (same
 // DFS order, same product order, same comparisons).  (Capacities: GF_* in amg_correct.h.)
 
-// The paths of one None run, found by the whole wave (wave_dfs, amg_wave_dfs.h): a path is accepted when it reaches
-// `e` with <= distance nodes and written to the LDS pool by lanes 0..len-1 at once, as a [run, len, nodes, dirs] record.
-struct GapVisit {
-  int e, distance, run, lane;
-  int *pool, *used;
-  int n_paths;
-  bool overflow;
-  __device__ __forceinline__ int enter(int, int L, int cur_node, int, int my_node, int my_dir) {
-    if (cur_node == e && L <= distance) {
-      const int off = *used;
-      if (off + 2 + 2 * L <= GF_POOL) {
-        if (lane == 0) {
-          pool[off] = run;
-          pool[off + 1] = L;
-        }
-        if (lane < L) {
-          pool[off + 2 + lane] = my_node;
-          pool[off + 2 + L + lane] = my_dir;
-        }
-      } else {
-        overflow = true;
-      }
-      wave_sync();
-      if (lane == 0) *used = off + 2 + 2 * L;
-      wave_sync();
-      ++n_paths;
-      return WD_RETREAT;
-    }
-    return L - 1 > distance ? WD_RETREAT : WD_EXPAND;
-  }
-};
-
-// returns the number of paths, -1 on pool overflow
-__device__ __forceinline__ int dfs_paths_wave(const GView& g, int s, int sdir, int e, int distance, int run, int* pool,
-                                              int* used, int lane) {
-  GapVisit v{e, distance, run, lane, pool, used, 0, false};
-  wave_dfs(g, s, sdir, lane, v);
-  return v.overflow ? -1 : v.n_paths;
-}
-
 // ---- path memo.  k_gap_queries: one LANE per re-threaded read walks the read's None runs on its live-window mask
 // (k_corr_classify kept it), looks up the three node words of each run and enters the question (start node, start
 // direction, end node) into an open-addressing table; the slot index is the question's id, the lane that created
 // the slot lists it.  k_gap_dfs answers every listed question once (the wave-cooperative search, dfs_paths_wave; result copied
-// to a global pool); k_corr_gapped_fast copies answers instead of searching.  Reads with more than 64 windows or
-// more than GF_MAXGAP runs take no part (gq[0] = -1: they search for themselves, as before).
-__device__ __forceinline__ unsigned long long gap_query_key(int s, int sdir, int e) {
-  return (1ull << 63) | ((unsigned long long)(unsigned int)s << 32) | ((unsigned long long)(unsigned int)e << 1) |
-         (sdir == 1 ? 1ull : 0ull);
-}
-
+// to a global pool) for k >= 8 and under AMG_GAP_DFS_WAVE=1; otherwise k_gap_dfs_lanes does (amg_gap_memo.hip, a lane per
+// question); k_corr_gapped_fast copies answers instead of searching.  Reads with more than 64 windows or more than
+// GF_MAXGAP runs take no part (gq[0] = -1: they search for themselves, as before).
 __global__ __launch_bounds__(256) void k_gap_queries(const GapRec* __restrict__ rec, long long n_gapped, int k,
                                                       const int* __restrict__ tok_node,
                                                       const signed char* __restrict__ tok_dir,
@@ -996,7 +948,11 @@ static int gap_memo(amg_ctx* c, const CorrSwitches& sw, const CorrArgs& a, CorrC
   if (qcap > 0x7fffffffull) return AMG_OK;  // (pool offsets are ints)
   AMGCHK(c->gm_pool.ensure((size_t)qcap * sizeof(int)));
   AMGCHK(c->gm_gene.ensure((size_t)qcap * sizeof(int)));
-  if (n_queries > 0)
+  if (n_queries > 0 && !sw.gap_dfs_wave && gap_dfs_lanes_fits(c->k))
+    gap_dfs_lanes_launch(c, c->gm_list.as<int>(), n_queries, c->gm_tab.as<unsigned long long>(),
+                         c->gm_ctr.as<unsigned long long>() + 1, qcap, c->gm_pool.as<int>(), c->gm_res.as<int4>(),
+                         c->gm_gene.as<int>());
+  else if (n_queries > 0)
     hipLaunchKernelGGL(k_gap_dfs, dim3((unsigned int)n_queries), dim3(64), 0, st, make_view(c), c->gm_list.as<int>(),
                        n_queries, c->gm_tab.as<unsigned long long>(), c->gm_ctr.as<unsigned long long>() + 1, qcap,
                        c->gm_pool.as<int>(), c->gm_res.as<int4>(), c->gm_gene.as<int>());
