@@ -5,6 +5,7 @@
 //   amg_correct_gapped.hip  re-threading of the reads with None runs      (stage correct_gapped)
 //   amg_gap_memo.hip        the path memo's search, a lane per question   (stage correct_gapped)
 //   amg_correct_nw.hip      position carry-over of the re-threaded reads  (stage correct_positions)
+//   amg_nw_probe.hip        amg_nw_probe: that stage alone on host arrays (test entry)
 //   amg_corrected.hip       the corrected set at the boundary (it gathers positions through CorrArgs' pools)
 #pragma once
 #include "amg_device.h"
@@ -67,6 +68,25 @@ __device__ __forceinline__ long long bcast_i64(long long v, int lane) {
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+}
+
+// inclusive prefix sum inside a DPP row of 16 lanes
+__device__ __forceinline__ int row_scan_incl(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  return v;
+}
+// inclusive prefix maximum over the 64 lanes of a wave (id: the identity, what a lane without a left neighbour takes)
+__device__ __forceinline__ int wave_prefix_max(int g, const int id) {
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x111, 0xf, 0xf, false));  // row_shr:1
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x112, 0xf, 0xf, false));  // row_shr:2
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x114, 0xf, 0xf, false));  // row_shr:4
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x118, 0xf, 0xf, false));  // row_shr:8
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x142, 0xa, 0xf, false));  // row_bcast:15
+  g = max(g, __builtin_amdgcn_update_dpp(id, g, 0x143, 0xc, 0xf, false));  // row_bcast:31
+  return g;
 }
 
 // ---- re-threading (amg_correct_gapped.hip)
@@ -152,6 +172,21 @@ enum {
 __device__ __forceinline__ bool nw_fast_ok(long long N, long long M) {
   return N <= NWF_MAX_N && M <= NWF_MAX_M && N > 0 && M > 0;
 }
+// what k_corr_nw keeps in LDS, and the global scratch of a pair beyond that (k_nw_sizes sizes it, k_corr_nw carves
+// it, amg_nw_probe refuses too much of it): the pointer matrix, a byte per cell; behind it the op list; at the next
+// 16 bytes three rolling anti-diagonals of N + 1 ints
+#define NW_LDS_N 1024       // rows and columns kept in LDS (rolling anti-diagonals, op list)
+#define NW_LDS_CELLS 16384  // pointer-matrix cells kept in LDS
+__host__ __device__ __forceinline__ bool nw_in_lds(long long N, long long M) {
+  return N <= NW_LDS_N && M <= NW_LDS_N && N * M <= NW_LDS_CELLS;
+}
+__host__ __device__ __forceinline__ long long nw_scratch_ops_at(long long N, long long M) { return N * M; }
+__host__ __device__ __forceinline__ long long nw_scratch_diag_at(long long N, long long M) {
+  return (N * M + N + M + 15) & ~15ll;
+}
+__host__ __device__ __forceinline__ long long nw_scratch_bytes(long long N, long long M) {
+  return nw_scratch_diag_at(N, M) + ((3 * (N + 1) * 4 + 15) & ~15ll);
+}
 
 struct __attribute__((aligned(16))) NwRec {
   int r, M, N, pad;
@@ -161,13 +196,11 @@ struct __attribute__((aligned(16))) NwRec {
 };
 
 struct NwArgs {
-  CorrArgs a;
+  CorrArgs a;        // (a.cls_final: the reads' final classes)
   const NwRec* rec;  // per gapped read, written by k_nw_sizes
   long long* o_gs;   // gene positions of the corrected set: the carry-over writes its reads' entries
   long long* o_ge;   // directly (no staging copy for the pack step to move again)
-  const int* gapped_reads;
   long long n_gapped;
-  const unsigned char* final_cls;
   const long long* big_off;  // per gapped read: byte offset of its global scratch (big reads only)
   unsigned char* big_buf;
   int allow_fast;            // 0: every read takes the general kernel (debugging / A-B switch)

@@ -528,14 +528,6 @@ __global__ __launch_bounds__(64, 8) void k_gap_dfs(GView g, const int* __restric
 // full size and by the fuzzers.
 #define GL_GROUP 16
 #define GL_THREADS 256
-__device__ __forceinline__ int row_scan_incl(int v) {  // inclusive prefix sum inside a DPP row of 16 lanes
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  return v;
-}
-
 __global__ __launch_bounds__(GL_THREADS) void k_corr_gapped_lean(GapArgs A, const int* __restrict__ qgene,
                                                                   unsigned char* __restrict__ left) {
   // per read and run: {first output index of the run's genes, their number, output - token shift behind them, where

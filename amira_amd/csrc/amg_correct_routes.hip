@@ -44,10 +44,7 @@ __global__ __launch_bounds__(256) void k_route_memo(long long n_queries, const i
 
 // one thread per gapped read: who carried its positions over.  This is the SIZING decision: what k_nw_sizes wrote — a
 // record with N > 0 is the fast kernel's, scratch bytes mean the general kernel away from its LDS matrix.  k_corr_nw
-// decides LDS against scratch again with its own copy of the `small` rule (one shared __device__ function changes
-// the code of both kernels, so the copies stay); if the two ever disagree this tally cannot see it, the comparison
-// of the carried-over positions with the oracle does (tests/test_gpu_correct_limits.py has reads on both sides of
-// either limit).
+// decides LDS against scratch by the same rule (nw_in_lds, amg_correct.h).
 __global__ __launch_bounds__(256) void k_route_nw(long long n_gapped, const NwRec* __restrict__ rec,
                                                   const long long* __restrict__ nw_size,
                                                   const unsigned char* __restrict__ final_cls,

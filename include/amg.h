@@ -520,6 +520,7 @@ int amg_count_probe(amg_ctx* ctx, int kind, int form, int32_t* ids, int64_t n, i
                     int64_t n_slots, int misalign, int flags, uint32_t* counts, int64_t* state);
 
 /* ---- tests: one position carry-over per pair of gene lists on host arrays ----------------------------
+ * (amg_nw_probe.hip.)
  * What the correct_positions stage of amg_correct_reads (amg_correct_nw.hip) makes of n_pairs pairs: pair p is the
  * corrected list x_tok[x_off[p] .. x_off[p + 1]) against the original list y_tok[y_off[p] .. y_off[p + 1]), whose genes
  * have the positions y_start / y_end (one entry per gene of y).  read_len: per pair, or NULL (no read lengths were

@@ -7,7 +7,7 @@ tests (tests/test_carry_over_cpu.py, tests/test_gpu_carry_over.py against amg_nw
                     thousands of the generated pairs by the CPU test)
   predicted_route   which of its routes the device must take for a pair: the two shortcut rules are the functions of
                     test_nw_shortcut_cpu.py (proved there against the reference's alignment), the limits are those of
-                    amg_correct.h / amg_correct_nw.hip restated
+                    amg_correct.h restated
   expected_totals   the three totals of the shape fetch that these sizes imply
   the generators    the pair sets of the GPU tests, from fixed seeds
 
@@ -20,7 +20,7 @@ import numpy as np
 from test_nw_shortcut_cpu import certificate_positions, shortcut_says_diagonal
 
 NWF_MAX_N, NWF_MAX_M = 128, 64          # amg_correct.h: what k_corr_nw_fast takes
-NW_LDS_N, NW_LDS_CELLS = 1024, 16384    # amg_correct_nw.hip: what k_corr_nw keeps in LDS
+NW_LDS_N, NW_LDS_CELLS = 1024, 16384    # amg_correct.h: what k_corr_nw keeps in LDS
 NO_FAST, NO_SHORTCUT, POOLED = 1, 2, 4  # flag bits of amg_nw_probe
 R_NONE, R_EQUAL, R_CERT, R_FILL, R_LDS, R_GLOBAL = range(6)
 

@@ -1,6 +1,6 @@
 """amg_correct_reads at the capacity limits where a read is handed from a faster kernel to a more general one
-(amg_correct.h: GF_MAXW, GF_MAXGAP, GF_POOL, GF_MAXCOMBO, GF_CAND, GM_INLINE, LEAN_CHUNK, NWF_MAX_M / NWF_MAX_N;
-amg_correct_nw.hip: NW_LDS_CELLS, NW_LDS_N; the path memo's pool and the general kernel's pool in corr_gapped).
+(amg_correct.h: GF_MAXW, GF_MAXGAP, GF_POOL, GF_MAXCOMBO, GF_CAND, GM_INLINE, LEAN_CHUNK, NWF_MAX_M / NWF_MAX_N,
+NW_LDS_CELLS, NW_LDS_N; the path memo's pool and the general kernel's pool in corr_gapped).
 
 Every case is a constructed read set.  It asserts (a) equality with the pinned Python oracle — graph arrays after
 build and after filter, corrected genes, read order and positions, then the rebuild from the corrected reads — and
