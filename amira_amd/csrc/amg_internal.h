@@ -8,11 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/amg.h"
-
-// ------------------------------------------------------------------ error plumbing
-extern thread_local std::string g_amg_err;
-int amg_fail(int code, const char* fmt, ...);
+#include "amg_host.h"  // include/amg.h, g_amg_err, amg_fail
 
 #define HIPCHK(call)                                                                   \
   do {                                                                                 \
