@@ -34,7 +34,8 @@
 // k * ceil(log2 2V) > 94 (k >= 7 on a 20 000-gene vocabulary): the key of the SAME 16-byte slots, claim ids and dense
 // per-claim arrays is a 94-bit fingerprint of the canonical tuple instead of the tuple itself (w1 = 63 bits, tag = 31).
 // Nothing else of the build changes; what a slot no longer says is read from the token stream where it is needed:
-//   * a node's tokens (k_x_assign_nodes*) are the window at its first-seen position, canonical by its direction bit;
+//   * a node's tokens (k_x_assign_nodes*) are the window at its first-seen position, canonical by its direction bit
+//     (so they are for every key scheme: node_tuples_from_reads);
 //   * every window's tuple is compared with the tuple at its claim's first-seen position (k_x_verify_fp: the creator's
 //     window — for the genome's nodes a few hundred kilobytes of the stream's head, L2-resident): two gene-mers that
 //     share a fingerprint raise ST_COLLISION and the build is repeated with the next seed (AMG_TEST_WEAK_FP cuts the
@@ -366,28 +367,45 @@ __device__ __forceinline__ long long x_rank_of(unsigned int t, const unsigned in
   return prefix[t >> 5] + (long long)__popc(w & ((1u << (t & 31)) - 1u));
 }
 
-__global__ void k_x_assign_nodes_ranked(const unsigned int* __restrict__ first2, long long n_nodes,
-                                        const unsigned int* __restrict__ bits, const long long* __restrict__ prefix,
-                                        const Slot16* __restrict__ tab, const unsigned int* __restrict__ slot_by_claim,
-                                        int k, int nbits, int two, int* __restrict__ final_of_claim,
-                                        int* __restrict__ node_tokens, long long* __restrict__ node_first,
-                                        unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_nodes) return;
-  if (x_first_inv(first2, c) == 0u) return;  // unclaimed
-  const unsigned int first = ~x_first_inv(first2, c);
-  const long long i = x_rank_of(first >> 1, bits, prefix);
-  final_of_claim[c] = (int)i;
-  node_first[i] = (long long)first;
-  node_alive[i] = 1;
-  if (nbits == 0) {  // fingerprint keys: the tuple is the window at the first-seen position, canonical by its direction bit
-    const long long f = (long long)(first >> 1);
-    for (int j = 0; j < k; ++j) node_tokens[i * k + j] = (first & 1u) ? flip - tokens[f + k - 1 - j] : tokens[f + j];
-    return;
+// A node's tuple is the window at its first-seen position, reversed and flipped when the first-seen's direction bit
+// (bit 0: ndir of k_nodes_m / k_nodes_v, whatever the key scheme) is set: the canonical tuple, read from the reads
+// rather than unpacked from the key's table slot (one random 16-byte read per claim of a table of hundreds of MB; the
+// claims of a wave were made by one tile, so their windows lie within the same 1 024 tokens).  A window lies inside its
+// read: f + k <= n_tokens.
+// The wave writes the 64 k tokens of its 64 nodes with a node's k tokens on neighbouring lanes: lane l of round m takes
+// token (l + 64 m) % k of the node of lane (l + 64 m) / k, so the nodes of consecutive ids — a wave's, nearly always —
+// leave as contiguous 256-byte stores (a lane writing its own k tokens puts the lanes of one store k ints apart).
+// Every lane of the wave calls; node < 0: this lane has none.
+__device__ __forceinline__ void node_tuples_from_reads(int* __restrict__ node_tokens, const int* __restrict__ tokens,
+                                                       int node, unsigned int first, int k, int flip) {
+  const unsigned int lane = threadIdx.x & 63u;
+  for (int m = 0; m < k; ++m) {
+    const unsigned int e = lane + 64u * (unsigned int)m;
+    const unsigned int q = e / (unsigned int)k, j = e - q * (unsigned int)k;  // (q < 64: e < 64 k)
+    const int nq = __shfl(node, (int)q, 64);
+    const unsigned int fq = __shfl(first, (int)q, 64);
+    if (nq < 0) continue;
+    const int* w = tokens + (long long)(fq >> 1);
+    node_tokens[(long long)nq * k + j] = (fq & 1u) ? flip - w[k - 1 - (int)j] : w[j];
   }
-  const Slot16 s = tab[slot_by_claim[c]];
-  const unsigned int tag = two ? (unsigned int)(s.w2 >> 32) : 0u;  // one-word keys keep the creator's first-seen there
-  for (int j = 0; j < k; ++j) node_tokens[i * k + j] = x_unpack(s.w1, tag, nbits, j);
+}
+
+__global__ __launch_bounds__(256) void k_x_assign_nodes_ranked(
+    const unsigned int* __restrict__ first2, long long n_nodes, const unsigned int* __restrict__ bits,
+    const long long* __restrict__ prefix, int k, int* __restrict__ final_of_claim, int* __restrict__ node_tokens,
+    long long* __restrict__ node_first, unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned int fi = c < n_nodes ? x_first_inv(first2, c) : 0u;  // 0: unclaimed (or past the end): no node
+  const unsigned int first = ~fi;
+  int node = -1;
+  if (fi != 0u) {
+    const long long i = x_rank_of(first >> 1, bits, prefix);
+    node = (int)i;
+    final_of_claim[c] = node;
+    node_first[i] = (long long)first;
+    node_alive[i] = 1;
+  }
+  node_tuples_from_reads(node_tokens, tokens, node, first, k, flip);
 }
 
 // An edge class recorded by the fused table pass is keyed by the CLAIM ids of its two nodes; here,
@@ -434,27 +452,19 @@ __global__ void k_x_sort_keys(const unsigned int* __restrict__ first2, long long
   vals[i] = (unsigned int)i;
 }
 
-__global__ void k_x_assign_nodes(const unsigned int* __restrict__ first_sorted,
-                                 const unsigned int* __restrict__ claim_sorted, long long n_nodes,
-                                 const Slot16* __restrict__ tab, const unsigned int* __restrict__ slot_by_claim,
-                                 int k, int bits, int two, int* __restrict__ final_of_claim,
-                                 int* __restrict__ node_tokens, long long* __restrict__ node_first,
-                                 unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_nodes) return;
-  const unsigned int c = claim_sorted[i];
-  final_of_claim[c] = (int)i;
-  node_first[i] = (long long)first_sorted[i];
-  node_alive[i] = 1;
-  if (bits == 0) {  // fingerprint keys (see k_x_assign_nodes_ranked)
-    const unsigned int first = first_sorted[i];
-    const long long f = (long long)(first >> 1);
-    for (int j = 0; j < k; ++j) node_tokens[i * k + j] = (first & 1u) ? flip - tokens[f + k - 1 - j] : tokens[f + j];
-    return;
+__global__ __launch_bounds__(256) void k_x_assign_nodes(
+    const unsigned int* __restrict__ first_sorted, const unsigned int* __restrict__ claim_sorted, long long n_nodes, int k,
+    int* __restrict__ final_of_claim, int* __restrict__ node_tokens, long long* __restrict__ node_first,
+    unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned int first = 0u;
+  if (i < n_nodes) {
+    first = first_sorted[i];
+    final_of_claim[claim_sorted[i]] = (int)i;
+    node_first[i] = (long long)first;
+    node_alive[i] = 1;
   }
-  const Slot16 s = tab[slot_by_claim[c]];
-  const unsigned int tag = two ? (unsigned int)(s.w2 >> 32) : 0u;  // one-word keys keep the creator's first-seen there
-  for (int j = 0; j < k; ++j) node_tokens[i * k + j] = x_unpack(s.w1, tag, bits, j);
+  node_tuples_from_reads(node_tokens, tokens, i < n_nodes ? (int)i : -1, first, k, flip);
 }
 
 // ------------------------------------------------------------------ components of a filtered build
@@ -1031,9 +1041,7 @@ int bx_nodes_rank(amg_ctx* c) {
     AMGCHK(x_rank_bitmap(c, c->x_first.as<unsigned int>(), S, 1));
     hipLaunchKernelGGL(k_x_assign_nodes_ranked, dim3(nblk(S, 256)), dim3(256), 0, st,
                        c->x_first.as<unsigned int>(), S,
-                       c->s1.as<unsigned int>(), c->s5.as<long long>(), c->node_tab.as<Slot16>(),
-                       c->x_slot.as<unsigned int>(), k, c->x_kbits, c->x_two ? 1 : 0,
-                       c->x_final.as<int>(), c->node_tokens.as<int>(),
+                       c->s1.as<unsigned int>(), c->s5.as<long long>(), k, c->x_final.as<int>(), c->node_tokens.as<int>(),
                        c->node_first.as<long long>(), c->node_alive.as<unsigned char>(), c->tokens.as<int>(), c->two_v - 1);
   } else if (D > 0) {
     c->rank_flags_clean = 0;  // (s0 is about to be reused by whoever comes next: nothing of it is known to be zero)
@@ -1043,8 +1051,7 @@ int bx_nodes_rank(amg_ctx* c) {
     AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s2.as<unsigned int>(), c->s3.as<unsigned int>(),
                              c->s4.as<unsigned int>(), (size_t)D, ilog2_ceil((uint64_t)T * 2 + 2) + 1));
     hipLaunchKernelGGL(k_x_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
-                       c->s4.as<unsigned int>(), D, c->node_tab.as<Slot16>(), c->x_slot.as<unsigned int>(),
-                       k, c->x_kbits, c->x_two ? 1 : 0, c->x_final.as<int>(),
+                       c->s4.as<unsigned int>(), D, k, c->x_final.as<int>(),
                        c->node_tokens.as<int>(), c->node_first.as<long long>(), c->node_alive.as<unsigned char>(),
                        c->tokens.as<int>(), c->two_v - 1);
   }

@@ -12,14 +12,48 @@ __global__ void k_filter_nodes(const unsigned int* __restrict__ cov, unsigned ch
 }
 
 // list_edges_to_remove (:505-521): coverage < minEdgeCoverage or a doomed endpoint
-__global__ void k_filter_edges(const int* __restrict__ src, const int* __restrict__ tgt,
-                               const unsigned int* __restrict__ cov,
-                               const unsigned char* __restrict__ node_alive,
-                               unsigned char* __restrict__ alive, long long n, unsigned int min_cov) {
-  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n || !alive[e]) return;
-  // (an edge's coverage is at least 1: with the usual threshold of 1 the coverage array is not read at all)
+// (an edge's coverage is at least 1: with the usual threshold of 1 the coverage array is not read at all)
+__device__ __forceinline__ void filter_edge(const int* __restrict__ src, const int* __restrict__ tgt,
+                                            const unsigned int* __restrict__ cov,
+                                            const unsigned char* __restrict__ node_alive,
+                                            unsigned char* __restrict__ alive, long long e, unsigned int min_cov) {
+  if (!alive[e]) return;
   if ((min_cov > 1 && cov[e] < min_cov) || !node_alive[src[e]] || !node_alive[tgt[e]]) alive[e] = 0;
+}
+
+// Four edges a thread (the edge arrays are allocations of their own, so edge 4 q is aligned for the wide loads): the
+// alive bytes arrive as one word, src and tgt as 16 bytes each, the eight node bytes are asked for together and the four
+// alive bytes leave as one word (a byte that was 0 stays 0).  The last n mod 4 edges take the scalar form.  One edge per
+// thread waited through alive -> src, tgt -> two node bytes -> store four times as often per byte moved.
+__global__ __launch_bounds__(256) void k_filter_edges(const int* __restrict__ src, const int* __restrict__ tgt,
+                                                      const unsigned int* __restrict__ cov,
+                                                      const unsigned char* __restrict__ node_alive,
+                                                      unsigned char* __restrict__ alive, long long n, unsigned int min_cov) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long e0 = 4 * q;
+  if (e0 >= n) return;
+  if (e0 + 4 > n) {
+    for (long long e = e0; e < n; ++e) filter_edge(src, tgt, cov, node_alive, alive, e, min_cov);
+    return;
+  }
+  const unsigned int a = reinterpret_cast<const unsigned int*>(alive)[q];
+  if (a == 0u) return;  // (nothing of the four is left to remove)
+  const int4 s = reinterpret_cast<const int4*>(src)[q];
+  const int4 t = reinterpret_cast<const int4*>(tgt)[q];
+  uint4 c = make_uint4(min_cov, min_cov, min_cov, min_cov);
+  if (min_cov > 1) c = reinterpret_cast<const uint4*>(cov)[q];
+  // (no load is under a test of its own: the ends of an edge that is dead already are not looked at, node 0 stands in)
+  const bool l0 = a & 0x000000ffu, l1 = a & 0x0000ff00u, l2 = a & 0x00ff0000u, l3 = a & 0xff000000u;
+  const unsigned int ns0 = node_alive[l0 ? s.x : 0], ns1 = node_alive[l1 ? s.y : 0], ns2 = node_alive[l2 ? s.z : 0],
+                     ns3 = node_alive[l3 ? s.w : 0];
+  const unsigned int nt0 = node_alive[l0 ? t.x : 0], nt1 = node_alive[l1 ? t.y : 0], nt2 = node_alive[l2 ? t.z : 0],
+                     nt3 = node_alive[l3 ? t.w : 0];
+  unsigned int keep = 0u;
+  if (ns0 && nt0 && c.x >= min_cov) keep |= 0x000000ffu;
+  if (ns1 && nt1 && c.y >= min_cov) keep |= 0x0000ff00u;
+  if (ns2 && nt2 && c.z >= min_cov) keep |= 0x00ff0000u;
+  if (ns3 && nt3 && c.w >= min_cov) keep |= 0xff000000u;
+  if ((a & keep) != a) reinterpret_cast<unsigned int*>(alive)[q] = a & keep;
 }
 
 // remove_node_from_reads (:442-461): one wave per read; windows of removed nodes become
@@ -69,7 +103,7 @@ static int apply_removals(amg_ctx* c, unsigned int min_edge_cov) {
   if (min_edge_cov > 1) live_lists_after_edge_deaths(c);  // (an edge may fall to its own coverage)
   else live_lists_after_node_deaths(c);
   if (c->n_edges > 0)
-    hipLaunchKernelGGL(k_filter_edges, dim3(nblk(c->n_edges, 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_filter_edges, dim3(nblk(c->n_edges, 4 * 256)), dim3(256), 0, st,
                        c->edge_src.as<int>(), c->edge_tgt.as<int>(), c->edge_cov.as<unsigned int>(),
                        c->node_alive.as<unsigned char>(), c->edge_alive.as<unsigned char>(),
                        c->n_edges, min_edge_cov);

@@ -358,6 +358,8 @@ int prim_exscan_emit_edges(amg_ctx* c, const unsigned long long* pkey, const uns
                            const unsigned long long* pfirst, size_t n_pairs, long long* total, int* e_src, int* e_tgt,
                            signed char* e_sdir, signed char* e_tdir, unsigned int* e_cov, unsigned char* e_alive,
                            const ClearList* side);
+int prim_exscan_live_edges(amg_ctx* c, const unsigned char* e_alive, const int* e_src, const signed char* e_sdir, size_t n_edges,
+                           long long* total, unsigned int* keys, unsigned int* edge_of, const ClearList* side);
 
 // one launch that zeroes up to 8 device ranges (a hipMemsetAsync is a kernel launch of its own: ~5 us
 // each, and a build issued ~40 of them); sizes are rounded up to 4 bytes — pad the allocations

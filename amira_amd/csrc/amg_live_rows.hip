@@ -27,9 +27,10 @@ void live_lists_after_edge_deaths(amg_ctx* c) {
 void live_lists_after_build(amg_ctx* c) { c->live_lists = LiveLists::Absent; }
 
 // ------------------------------------------------------------------ the lists from the live edges
-// Flag + scan squeezes the removed edges out in edge order (k_live_keys: the dense list of live edges with their rows);
-// the rows are then made from that list WITHOUT a sort (a library radix sort of a few ten thousand pairs is a dozen
-// launches).  The live edges of a row are few (one side of one node), so:
+// One scan over the edges' alive bytes squeezes the removed edges out in edge order: its emitter writes the dense list of
+// live edges with their rows itself (prim_exscan_live_edges; no position per edge is written and read back).  The rows
+// are then made from that list WITHOUT a sort (a library radix sort of a few ten thousand pairs is a dozen launches).
+// The live edges of a row are few (one side of one node), so:
 //   k_lr_count   every live edge adds 1 to its row's counter                          (rows zeroed before)
 //   k_lr_alloc   every live edge takes a ticket of its row; ticket 0 reserves the row's stretch of the entry
 //                array — stretches are handed out per workgroup with ONE atomicAdd (their order is irrelevant)
@@ -39,16 +40,6 @@ void live_lists_after_build(amg_ctx* c) { c->live_lists = LiveLists::Absent; }
 //                and the row record; rows longer than a wave's 64 lanes are left to k_lr_long (hub nodes)
 // The walkers then never touch a dead edge (a hub node of an uncorrected graph lists hundreds of them), and the lists
 // of the removed edges are never made at all.
-__global__ void k_live_keys(const unsigned char* __restrict__ e_alive, const int* __restrict__ e_src,
-                            const signed char* __restrict__ e_sdir, const long long* __restrict__ pos,
-                            long long n_edges, unsigned int* __restrict__ keys, unsigned int* __restrict__ vals) {
-  long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_edges || !e_alive[e]) return;
-  const long long o = pos[e];
-  keys[o] = adj_row_of(e_src[e], e_sdir[e]);
-  vals[o] = (unsigned int)e;
-}
-
 __global__ void k_lr_count(const unsigned int* __restrict__ keys, long long n_live, int4* __restrict__ lrows) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_live) atomicAdd(&lrows[keys[i]].y, 1);
@@ -195,31 +186,31 @@ int ensure_live_adj(amg_ctx* c) {
   }
   const long long rows = 2 * c->n_nodes, E = c->n_edges;
   AMGCHK(c->ladj_rows.ensure((size_t)(rows + 2) * sizeof(int4)));
-  AMGCHK(c->ladj_pos.ensure((size_t)(E + 2) * sizeof(long long)));
+  // the dense list {row, edge id}: two arrays of E + 2 words, and behind them the number of live edges
+  AMGCHK(c->ladj_pos.ensure((size_t)(E + 3) * sizeof(long long)));
+  unsigned int* keys = c->ladj_pos.as<unsigned int>();
+  unsigned int* edge_of = keys + (E + 2);
+  long long* d_total = c->ladj_pos.as<long long>() + (E + 2);
   unsigned long long* ctr = c->status.as<unsigned long long>() + ST_COMPACT_A;  // [0] entries handed out, [1] long rows
   {  // the rows and counters are zeroed by the scan's workgroups
     ClearList cl;
     cl.add(c->ladj_rows.p, (size_t)(rows + 2) * sizeof(int4));
     cl.add(ctr, 2 * sizeof(unsigned long long));
-    AMGCHK(prim_exscan_bytes_set(c, c->edge_alive.as<unsigned char>(), c->ladj_pos.as<long long>(), (size_t)E, &cl));
+    AMGCHK(prim_exscan_live_edges(c, c->edge_alive.as<unsigned char>(), c->edge_src.as<int>(), c->edge_sdir.as<signed char>(),
+                                  (size_t)E, d_total, keys, edge_of, &cl));
   }
   long long total = 0;
   {
     FetchList l;
-    l.add(c->ladj_pos.as<long long>() + E);
+    l.add(d_total);
     AMGCHK(fetch(c, l, reinterpret_cast<unsigned long long*>(&total)));
   }
   AMGCHK(c->ladj.ensure((size_t)(total + 1) * sizeof(int2)));
-  AMGCHK(c->ladj_keys.ensure(5 * (size_t)(total + 2) * sizeof(unsigned int)));
-  unsigned int* keys = c->ladj_keys.as<unsigned int>();
-  unsigned int* edge_of = keys + (total + 2);
-  unsigned int* tick = edge_of + (total + 2);
+  AMGCHK(c->ladj_keys.ensure(3 * (size_t)(total + 2) * sizeof(unsigned int)));
+  unsigned int* tick = c->ladj_keys.as<unsigned int>();
   unsigned int* tmp = tick + (total + 2);
   unsigned int* long_rows = tmp + (total + 2);
   if (total > 0) {
-    hipLaunchKernelGGL(k_live_keys, dim3(nblk(E, 256)), dim3(256), 0, st, c->edge_alive.as<unsigned char>(),
-                       c->edge_src.as<int>(), c->edge_sdir.as<signed char>(), c->ladj_pos.as<long long>(), E, keys,
-                       edge_of);
     hipLaunchKernelGGL(k_lr_count, dim3(nblk(total, 256)), dim3(256), 0, st, keys, total, c->ladj_rows.as<int4>());
     hipLaunchKernelGGL(k_lr_alloc, dim3(nblk(total, 256 * LR_PER)), dim3(256), 0, st, keys, total, c->ladj_rows.as<int4>(),
                        tick, ctr);

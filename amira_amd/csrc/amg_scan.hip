@@ -12,7 +12,7 @@
 //     epoch is not the current scan's is simply "not there yet" (the buffer is zeroed when the 14-bit epoch wraps);
 //   * the first wave of a tile looks back 64 predecessors at a time until it meets an inclusive prefix.
 // Values are sums of non-negative counts below 2^48.
-#include "amg_device.h"
+#include "amg_rows.h"
 
 #define SC_THREADS 512                  // 8 waves per workgroup
 #define SC_ROWS 16                       // rows of 64 per wave: a wave scans 1024 consecutive elements
@@ -38,7 +38,7 @@ __device__ __forceinline__ unsigned long long sc_word(unsigned int state, unsign
 //   LoadArrN<T>, LoadNonzero, LoadByteSet   in[i] / (in[i] != 0) with the terminator built in
 // What happens to the exclusive prefix of element i of the first array is an EMITTER's business: EmitOut stores it in
 // out[i]; a compaction's emitter scatters element i to its place itself, so no position array is written and read back
-// by a kernel of its own (EmitEdges).  A scan may also zero a few ranges no scan element touches (`side`,
+// by a kernel of its own (EmitEdges, EmitLiveKeys).  A scan may also zero a few ranges no scan element touches (`side`,
 // grid-stride over its workgroups, after their tiles are published): the clear_many launch before it goes away.
 // Two scans that do not depend on each other travel as ONE launch (k_exscan<LA, LB>: tiles [0, tiles_a) scan the first
 // array, the tiles behind them the second, whose look-back stops at its own first tile).
@@ -169,12 +169,13 @@ __device__ __forceinline__ void load_rows(const L& ld, long long w0, long long n
   }
 }
 
-// An emitter's loads (pre) are issued for all rows of a wave while the tile looks back; operator() stores.
+// An emitter's loads (pre) are issued for all rows of a wave while the tile looks back; operator() stores (val: the
+// value element i was scanned with).
 struct EmitOut {
   long long* out;
   struct Pre {};
   __device__ __forceinline__ Pre pre(long long) const { return Pre{}; }
-  __device__ __forceinline__ void operator()(long long i, unsigned long long excl, const Pre&) const {
+  __device__ __forceinline__ void operator()(long long i, unsigned long long excl, const Pre&, unsigned long long) const {
     out[i] = (long long)excl;
   }
 };
@@ -200,7 +201,7 @@ struct EmitEdges {
     const long long j = i < n_pairs ? i : 0;  // (the terminator loads class 0: unused)
     return Pre{pkey[j], pfirst[j], pcnt[j]};
   }
-  __device__ __forceinline__ void operator()(long long i, unsigned long long excl, const Pre& p) const {
+  __device__ __forceinline__ void operator()(long long i, unsigned long long excl, const Pre& p, unsigned long long) const {
     if (i >= n_pairs) {
       total[0] = (long long)excl;
       return;
@@ -220,6 +221,29 @@ struct EmitEdges {
       e_src[e + 1] = Y; e_tgt[e + 1] = X; e_sdir[e + 1] = (signed char)-dY;
       e_tdir[e + 1] = (signed char)-dX; e_cov[e + 1] = cnt; e_alive[e + 1] = 1;
     }
+  }
+};
+// live edges -> the dense list of their rows and ids (the scan of LoadByteSet over the edges' alive bytes): live edge i
+// writes {its row, i} at excl, a dead edge nothing; total[0] = the number of live edges (element n_edges).  Nothing is
+// written at or beyond total.  An edge's source is loaded under the alive test: a few edges in a thousand survive the
+// filter of a first graph, and loading the sources of all of them would be the pass over the edges this saves.
+struct EmitLiveKeys {
+  const int* e_src;
+  const signed char* e_sdir;
+  long long n_edges;
+  long long* total;
+  unsigned int* keys;
+  unsigned int* edge_of;
+  struct Pre {};
+  __device__ __forceinline__ Pre pre(long long) const { return Pre{}; }
+  __device__ __forceinline__ void operator()(long long i, unsigned long long excl, const Pre&, unsigned long long val) const {
+    if (i >= n_edges) {
+      total[0] = (long long)excl;
+      return;
+    }
+    if (val == 0ull) return;
+    keys[excl] = adj_row_of(e_src[i], e_sdir[i]);
+    edge_of[excl] = (unsigned int)i;
   }
 };
 template <class Load, class LoadB, class Emit>
@@ -319,7 +343,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_exscan(Load load, Emit emit_a, l
       if (second)
         out_b[i] = (long long)(base + inc[r] - x[r]);
       else
-        emit_a(i, base + inc[r] - x[r], pre[r]);
+        emit_a(i, base + inc[r] - x[r], pre[r], x[r]);
     }
   }
   if (side.n) clear_args_part(side, blockIdx.x, gridDim.x);
@@ -426,6 +450,14 @@ int prim_exscan_emit_edges(amg_ctx* c, const unsigned long long* pkey, const uns
                      n_pairs + 1, LoadNone{}, nullptr, 0, side);
 }
 
+// live edges -> {row, edge id} pairs in edge order at keys / edge_of, *total = their number; side: ranges zeroed on the way
+int prim_exscan_live_edges(amg_ctx* c, const unsigned char* e_alive, const int* e_src, const signed char* e_sdir, size_t n_edges,
+                           long long* total, unsigned int* keys, unsigned int* edge_of, const ClearList* side) {
+  return exscan_emit(c, LoadByteSet{e_alive, (long long)n_edges},
+                     EmitLiveKeys{e_src, e_sdir, (long long)n_edges, total, keys, edge_of}, n_edges + 1, LoadNone{}, nullptr, 0,
+                     side);
+}
+
 // ------------------------------------------------------------------ amg_scan_probe (tests: one scan on host arrays)
 extern "C" int amg_scan_probe(amg_ctx* c, int kind, const void* in, int64_t n, int64_t* out, void* aux) {
   if (!c || n < 0 || (n > 0 && !in) || !out) return amg_fail(AMG_E_ARG, "scan_probe: bad arguments");
@@ -437,6 +469,7 @@ extern "C" int amg_scan_probe(amg_ctx* c, int kind, const void* in, int64_t n, i
     case 3: in_bytes = 2 * (size_t)n; aux_bytes = 2 * (size_t)n; break;            // apply kill; aux: kill, alive after
     case 4: in_bytes = 4 * (size_t)n; out_words = 2 * ((size_t)n + 1); break;      // keep (len != 0) and len
     case 5: in_bytes = 20 * (size_t)n; out_words = 1; aux_bytes = 30 * (size_t)n; break;  // edges of classes
+    case 6: in_bytes = 6 * (size_t)n; out_words = 1; aux_bytes = 8 * (size_t)n; break;     // live edges: src, alive, sdir
     default: return amg_fail(AMG_E_ARG, "scan_probe: unknown kind %d", kind);
   }
   char* d = nullptr;
@@ -489,6 +522,13 @@ extern "C" int amg_scan_probe(amg_ctx* c, int kind, const void* in, int64_t n, i
                                     reinterpret_cast<unsigned int*>(din + 16 * (size_t)n),
                                     reinterpret_cast<unsigned long long*>(din + 8 * (size_t)n), (size_t)n, dout, src, tgt,
                                     sdir, tdir, cov, alive, nullptr);
+        break;
+      }
+      case 6: {
+        unsigned int* keys = reinterpret_cast<unsigned int*>(daux);
+        rc = prim_exscan_live_edges(c, reinterpret_cast<unsigned char*>(din + 4 * (size_t)n), reinterpret_cast<int*>(din),
+                                    reinterpret_cast<signed char*>(din + 5 * (size_t)n), (size_t)n, dout, keys, keys + n,
+                                    nullptr);
         break;
       }
     }

@@ -500,7 +500,9 @@ int amg_set_timing(amg_ctx* ctx, int on);
  * 3: in = kill[n] then alive[n] (uint8): out[i] = live killed nodes before i; aux = kill[n], alive[n] after.
  * 4: in = uint32 len[n]: out[0 .. n] = exscan(len != 0), out[n + 1 .. 2n + 1] = exscan(len).
  * 5: in = keys[n] (uint64), first[n] (uint64), cnt[n] (uint32): out[0] = directed edges, aux = src, tgt (int32),
- *    cov (uint32), sdir, tdir (int8), alive (uint8) over 2n edges each. */
+ *    cov (uint32), sdir, tdir (int8), alive (uint8) over 2n edges each.
+ * 6: in = src[n] (int32), alive[n] (uint8), sdir[n] (int8): out[0] = live edges, aux = keys[n], edge_of[n] (uint32):
+ *    the row and the id of every live edge in edge order; nothing is written from out[0] on. */
 int amg_scan_probe(amg_ctx* ctx, int kind, const void* in, int64_t n, int64_t* out, void* aux);
 
 /* ---- tests: one count of the coverage counting sweeps on host arrays ------------------------------
