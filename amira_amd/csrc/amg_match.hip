@@ -29,6 +29,7 @@ struct MatchArgs {
   int lds_words;              // words of has_bits staged in LDS (0: tested in global memory)
   unsigned long long* hits;   // nullptr: count only
   unsigned int* wave_count;   // count launch: hits of every wave of the grid
+  unsigned long long* too_long;  // count launch: set to 1 by a wave that met a row of more than 2^POS_BITS symbols
   const long long* wave_base; // fill launch (same grid): where every wave's hits begin
   unsigned long long cap;
 };
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
   const long long wave0 = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long n_waves = (long long)gridDim.x * (blockDim.x >> 6);
   unsigned long long counted = 0;  // hits of this wave so far (fill launch: its next place is wave_base + counted)
+  bool beyond = false;             // a row of this wave holds positions the packed hits have no bits for
   const unsigned long long my_base = A.hits ? (unsigned long long)A.wave_base[wave0] : 0ull;
   // MATCH_BATCH reads per iteration: their offsets and first 64 symbols are loaded for all of them before any is
   // looked at (a wave that walks one read at a time is bound by the chain offsets -> symbols of that one read); a read
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
       const long long r = rb + q;
       bt0[q] = r < A.n_reads ? A.read_off[r] : 0;
       blen[q] = r < A.n_reads ? A.read_off[r + 1] - bt0[q] - A.tail : 0;
+      beyond |= blen[q] > (1ll << POS_BITS);
     }
 #pragma unroll
     for (int q = 0; q < MATCH_BATCH; ++q) bsym[q] = lane < blen[q] ? A.seq[bt0[q] + lane] : -1;
@@ -121,6 +124,7 @@ __global__ __launch_bounds__(256) void k_match(MatchArgs A) {
   if (!A.hits) {
     for (int d = 32; d > 0; d >>= 1) counted += __shfl_down(counted, d, 64);
     if (lane == 0) A.wave_count[wave0] = (unsigned int)counted;
+    if (lane == 0 && beyond) *A.too_long = 1ull;  // (every wave that writes it writes the same word)
   }
 }
 
@@ -252,19 +256,28 @@ extern "C" int amg_match_patterns(amg_ctx* c, int which, const int32_t* pat, con
   const long long n_waves = (long long)match_blocks * 4;
   AMGCHK(c->match_wave.ensure((size_t)(n_waves + 2) * (sizeof(unsigned int) + sizeof(long long)) + 16));
   long long* wave_base = c->match_wave.as<long long>();
-  unsigned int* wave_count = reinterpret_cast<unsigned int*>(wave_base + (n_waves + 2));
+  // the flag word of the row lengths lies in front of the counts: one memset clears both
+  unsigned long long* too_long = reinterpret_cast<unsigned long long*>(wave_base + (n_waves + 2));
+  unsigned int* wave_count = reinterpret_cast<unsigned int*>(too_long + 1);
   A.wave_count = wave_count;
+  A.too_long = too_long;
   A.wave_base = wave_base;
-  HIPCHK(hipMemsetAsync(wave_count, 0, (size_t)(n_waves + 1) * sizeof(unsigned int), st));
+  HIPCHK(hipMemsetAsync(too_long, 0, sizeof(unsigned long long) + (size_t)(n_waves + 1) * sizeof(unsigned int), st));
   stage_begin(c, "match_count");  // (the stage is the kernel alone: bench.py prices it against the HBM roofline)
   if (c->n_reads > 0) hipLaunchKernelGGL(k_match, dim3(match_blocks), dim3(256), lds_bytes, st, A);
   stage_end(c);
   AMGCHK(prim_exscan_u32_to_i64(c, wave_count, wave_base, (size_t)n_waves + 1));
   unsigned long long total = 0;
   {
+    unsigned long long got[2] = {0, 0};
     FetchList l;
     l.add(wave_base + n_waves);
-    AMGCHK(fetch(c, l, &total));
+    l.add(too_long);
+    AMGCHK(fetch(c, l, got));
+    // a hit is packed with POS_BITS bits of position: a longer row would put its positions into the read field
+    if (got[1])
+      return amg_fail(AMG_E_ARG, "amg_match_patterns: a read holds more than %d searched symbols", 1 << POS_BITS);
+    total = got[0];
   }
   AMGCHK(c->match_read.ensure((size_t)(total + 1) * sizeof(int)));
   AMGCHK(c->match_pos.ensure((size_t)(total + 1) * sizeof(int)));

@@ -246,7 +246,8 @@ int amg_set_reads_from_corrected(amg_ctx* dst, amg_ctx* src);
 /* patterns are CSR token lists; each is searched forward in every read's TOKENS
  * (which = 0) or NODE ids (which = 1).  Two-call: hit_read == NULL returns counts in
  * hit_offsets[n_pat + 1]; then (hit_read, hit_pos) get one entry per occurrence,
- * ordered by (pattern, read, position). */
+ * ordered by (pattern, read, position).  At most 65 535 patterns a call, and no searched row (a read's tokens, or its
+ * windows for which = 1) longer than 2^20 symbols: AMG_E_ARG otherwise, and no hits. */
 int amg_match_patterns(amg_ctx* ctx, int which, const int32_t* pat, const int64_t* pat_offsets,
                        int64_t n_pat, int64_t* hit_offsets, int32_t* hit_read,
                        int32_t* hit_pos);
