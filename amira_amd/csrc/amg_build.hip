@@ -7,7 +7,9 @@
 //   read statistics      bs_read_stats, here
 //   nodes, edge classes  by key scheme (build_impl chooses, bx_applicable):
 //     exact tuple keys, or verified 94-bit fingerprints of a tuple that does not fit, in 16-byte slots with claim ids:
-//       amg_build_x.hip  bx_nodes / bx_nodes_filtered, bx_edges
+//       amg_build_x.hip         the table passes (bx_nodes_upsert, bx_edges_upsert)
+//       amg_build_x_claims.hip  per claim: coverage, the fused filter, ranking; bx_nodes / bx_nodes_filtered, bx_edges
+//       amg_build_x_comp.hip    a filtered build's components and touched reads
 //     verified 64-bit fingerprints in 32-byte slots (2^29 tokens and more, a merged build whose tuple does not fit a slot,
 //     AMG_KEY_MODE=fp, AMG_COUNT_INLINE, a fitting tuple under the weak-fingerprint hook):
 //       amg_build_fp.hip bs_nodes_pass        local windows -> local node table (+ compaction list in s1 / s3)
@@ -159,7 +161,6 @@ BuildSwitches read_build_switches() {
   if (const char* e = getenv("AMG_KEY_MODE")) sw.key_fp = e[0] == 'f';
   sw.node_buckets = !is_zero(getenv("AMG_NODE_BUCKETS"));
   sw.generic_k = getenv("AMG_X_GENERIC_K") != nullptr;
-  sw.rank_sort = getenv("AMG_X_RANK_SORT") != nullptr;
   if (const char* e = getenv("AMG_EDGE_LONE")) sw.edge_lone = atoi(e) != 0;
   sw.edge_home = !is_zero(getenv("AMG_EDGE_HOME"));
   sw.no_derive = getenv("AMG_NO_DERIVE") != nullptr;
@@ -228,11 +229,11 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
     int r;
     if (exact && min_node_cov > 0) {
       r = bx_nodes_filtered(c, k, min_node_cov, &which);
-      if (r == AMG_OK) r = bx_edges(c, &which, min_edge_cov);
+      if (r == AMG_OK) r = bx_edges(c, &which, PassCaller::FilteredBuild, min_edge_cov);
       *fused = true;
     } else if (exact) {
       r = bx_nodes(c, k, &which);
-      if (r == AMG_OK) r = bx_edges(c, &which);
+      if (r == AMG_OK) r = bx_edges(c, &which, PassCaller::PlainBuild, 0);
     } else {
       r = bs_nodes_pass(c, k, &which);
       if (r == AMG_OK) r = bs_nodes_rank_local(c);

@@ -1,5 +1,8 @@
-// amg_build_x.hip — the single-GPU build in 16-byte slots with claim ids: EXACT tuple keys, or verified 94-bit
-// fingerprints of the tuple in the same slots.
+// amg_build_x.hip — the build in 16-byte slots with claim ids: EXACT tuple keys, or verified 94-bit fingerprints of the
+// tuple in the same slots.  This unit holds the two TABLE PASSES (windows -> node claims, adjacencies -> edge-class
+// claims: bx_nodes_upsert, bx_edges_upsert) and their claim plan; what is then done per claim — coverage, the fused
+// filter, ranking — and the drivers bx_nodes / bx_nodes_filtered / bx_edges are amg_build_x_claims.hip's, a filtered
+// build's components and read flags amg_build_x_comp.hip's.
 //
 // Same result as the 32-byte fingerprint path of amg_build_fp.hip (GeneMerGraph.__init__, reference construct_graph.py:31-102),
 // different bookkeeping.  The canonical k-tuple itself is the key whenever it fits 94 bits (k * ceil(log2(2V)) <= 94:
@@ -34,8 +37,8 @@
 // k * ceil(log2 2V) > 94 (k >= 7 on a 20 000-gene vocabulary): the key of the SAME 16-byte slots, claim ids and dense
 // per-claim arrays is a 94-bit fingerprint of the canonical tuple instead of the tuple itself (w1 = 63 bits, tag = 31).
 // Nothing else of the build changes; what a slot no longer says is read from the token stream where it is needed:
-//   * a node's tokens (k_x_assign_nodes*) are the window at its first-seen position, canonical by its direction bit
-//     (so they are for every key scheme: node_tuples_from_reads);
+//   * a node's tokens (k_x_assign_nodes_ranked) are the window at its first-seen position, canonical by its direction bit
+//     (so they are for every key scheme: node_tuples_from_reads, amg_build_x_claims.hip);
 //   * every window's tuple is compared with the tuple at its claim's first-seen position (k_x_verify_fp: the creator's
 //     window — for the genome's nodes a few hundred kilobytes of the stream's head, L2-resident): two gene-mers that
 //     share a fingerprint raise ST_COLLISION and the build is repeated with the next seed (AMG_TEST_WEAK_FP cuts the
@@ -292,249 +295,6 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_nodes_m(
   }
 }
 
-// ---- build with the coverage filter applied on the way (amg_build_filtered): claims below the threshold are
-// taken out of the claim space (first-seen words zeroed = "unclaimed", which every ranking kernel skips) before
-// anything is ranked, so only the survivors get ids, arrays, edges
-__global__ void k_x_drop_claims(const unsigned int* __restrict__ cnt, long long n, unsigned int min_cnt,
-                                unsigned int* __restrict__ first2, int* __restrict__ final_of_claim,
-                                unsigned long long* __restrict__ n_kept, unsigned int* __restrict__ first_all) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  bool keep = false;
-  if (c < n) {
-    if (first_all) first_all[c] = x_first_inv(first2, c);  // component labels are those of the UNFILTERED graph
-    keep = cnt[c] >= min_cnt && x_first_inv(first2, c) != 0u;
-    if (!keep) {
-      first2[2 * c] = 0u;
-      first2[2 * c + 1] = 0u;
-      if (final_of_claim) final_of_claim[c] = -2;  // windows of a dropped node read None (remove_node_from_reads)
-    }
-  }
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_kept, (unsigned long long)__popcll(m));
-}
-
-// tagged != nullptr: claim -> node id | AMG_SINGLE_BIT where the node's coverage is 1 (what k_edges_v<.., LONE> reads)
-__global__ void k_x_cov_from_claims(const unsigned int* __restrict__ cnt, const unsigned int* __restrict__ first2,
-                                    const int* __restrict__ final_of_claim, long long n,
-                                    unsigned int* __restrict__ node_cov, int* __restrict__ tagged) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n) return;
-  const int id = final_of_claim[c];
-  const bool used = x_first_inv(first2, c) != 0u;
-  if (tagged) tagged[c] = (used && id >= 0 && cnt[c] == 1u) ? (int)((unsigned int)id | AMG_SINGLE_BIT) : id;
-  if (used) node_cov[id] = cnt[c];
-}
-
-// reads that lost a window to the filter join _readsToCorrect (remove_node_from_reads :442-461).  Sixteen lanes per
-// read, four loads per lane in flight: a wave per read kept ONE 240-byte load in flight and ran at 1.2 TB/s.
-#define FD_READS 16  // reads per 256-thread workgroup
-__global__ __launch_bounds__(256) void k_x_flag_dead_reads(const int* __restrict__ tok_node,
-                                                            const long long* __restrict__ read_off, long long n_reads,
-                                                            unsigned char* __restrict__ read_fix) {
-  const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
-  const long long r = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + grp;
-  const bool have = r < n_reads;
-  const long long a = have ? read_off[r] : 0, b = have ? read_off[r + 1] : 0;
-  int v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = a + sub + 16 * j < b ? tok_node[a + sub + 16 * j] : 0;
-  bool hit = v[0] == -2 || v[1] == -2 || v[2] == -2 || v[3] == -2;
-  for (long long t = a + 64 + sub; t < b; t += 16) hit = hit || (tok_node[t] == -2);  // reads longer than 64 genes
-  const unsigned long long m = __ballot(hit);
-  if (have && sub == 0 && ((m >> (grp * 16)) & 0xffffull)) read_fix[r] = 1;
-}
-
-// ---- ranking by first-seen without a sort.  A token
-// position opens at most one window / adjacency, so the first-seen token indices of the claims are
-// distinct: set one bit per claim in a bitmap over the tokens, prefix-count the bitmap words, and
-// the rank of a claim is the number of bits before its own.  (A radix sort of 0.5 - 1 M pairs
-// costs ~10 launches and ~0.2 ms however small the input; this costs ~0.06 ms.)
-// (one BYTE per token first, set with plain stores: 5.4 M scattered atomicOr on bitmap words ran at the
-// memory-side atomic rate, 0.2 ms per ranking of the first build; the bytes are folded into the
-// bitmap words by the pass that counts them)
-__global__ void k_x_rank_setflags(const unsigned int* __restrict__ first2, long long n, int shift,
-                                  unsigned char* __restrict__ flags) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const unsigned int fi = x_first_inv(first2, i);
-  if (fi == 0u) return;  // a claim id nobody took (the chunked shards leave holes: XShard)
-  flags[(~fi) >> shift] = 1;
-}
-
-__device__ __forceinline__ long long x_rank_of(unsigned int t, const unsigned int* __restrict__ bits,
-                                               const long long* __restrict__ prefix) {
-  const unsigned int w = bits[t >> 5];
-  return prefix[t >> 5] + (long long)__popc(w & ((1u << (t & 31)) - 1u));
-}
-
-// A node's tuple is the window at its first-seen position, reversed and flipped when the first-seen's direction bit
-// (bit 0: ndir of k_nodes_m / k_nodes_v, whatever the key scheme) is set: the canonical tuple, read from the reads
-// rather than unpacked from the key's table slot (one random 16-byte read per claim of a table of hundreds of MB; the
-// claims of a wave were made by one tile, so their windows lie within the same 1 024 tokens).  A window lies inside its
-// read: f + k <= n_tokens.
-// The wave writes the 64 k tokens of its 64 nodes with a node's k tokens on neighbouring lanes: lane l of round m takes
-// token (l + 64 m) % k of the node of lane (l + 64 m) / k, so the nodes of consecutive ids — a wave's, nearly always —
-// leave as contiguous 256-byte stores (a lane writing its own k tokens puts the lanes of one store k ints apart).
-// Every lane of the wave calls; node < 0: this lane has none.
-__device__ __forceinline__ void node_tuples_from_reads(int* __restrict__ node_tokens, const int* __restrict__ tokens,
-                                                       int node, unsigned int first, int k, int flip) {
-  const unsigned int lane = threadIdx.x & 63u;
-  for (int m = 0; m < k; ++m) {
-    const unsigned int e = lane + 64u * (unsigned int)m;
-    const unsigned int q = e / (unsigned int)k, j = e - q * (unsigned int)k;  // (q < 64: e < 64 k)
-    const int nq = __shfl(node, (int)q, 64);
-    const unsigned int fq = __shfl(first, (int)q, 64);
-    if (nq < 0) continue;
-    const int* w = tokens + (long long)(fq >> 1);
-    node_tokens[(long long)nq * k + j] = (fq & 1u) ? flip - w[k - 1 - (int)j] : w[j];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_x_assign_nodes_ranked(
-    const unsigned int* __restrict__ first2, long long n_nodes, const unsigned int* __restrict__ bits,
-    const long long* __restrict__ prefix, int k, int* __restrict__ final_of_claim, int* __restrict__ node_tokens,
-    long long* __restrict__ node_first, unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
-  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned int fi = c < n_nodes ? x_first_inv(first2, c) : 0u;  // 0: unclaimed (or past the end): no node
-  const unsigned int first = ~fi;
-  int node = -1;
-  if (fi != 0u) {
-    const long long i = x_rank_of(first >> 1, bits, prefix);
-    node = (int)i;
-    final_of_claim[c] = node;
-    node_first[i] = (long long)first;
-    node_alive[i] = 1;
-  }
-  node_tuples_from_reads(node_tokens, tokens, node, first, k, flip);
-}
-
-// An edge class recorded by the fused table pass is keyed by the CLAIM ids of its two nodes; here,
-// where the classes are ranked, key and orientation bit are re-expressed in final node ids:
-// key = (sign, smaller id, larger id + 1), bit 0 of first-seen = "the first event ran smaller -> larger"
-__device__ __forceinline__ void pair_to_final(unsigned long long& key, unsigned int& first,
-                                              const int* __restrict__ fin) {
-  const unsigned int lo_c = (unsigned int)((key >> 32) & 0x7fffffffull);
-  const unsigned int hi_c = (unsigned int)(key & 0xffffffffull) - 1u;
-  const bool a_is_lo = (first & 1u) != 0u;
-  const unsigned int X = (unsigned int)fin[a_is_lo ? lo_c : hi_c], Y = (unsigned int)fin[a_is_lo ? hi_c : lo_c];
-  const unsigned int lo = X < Y ? X : Y, hi = X < Y ? Y : X;
-  key = (key & (1ull << 63)) | ((unsigned long long)lo << 32) | (unsigned long long)(hi + 1u);
-  first = (first & ~1u) | (X == lo ? 1u : 0u);
-}
-
-__global__ void k_x_gather_pairs_ranked(const unsigned int* __restrict__ first2, long long n_pairs,
-                                        const unsigned int* __restrict__ bits, const long long* __restrict__ prefix,
-                                        const Slot16* __restrict__ etab, const unsigned int* __restrict__ slot_by_claim,
-                                        const unsigned int* __restrict__ cnt_by_claim,
-                                        unsigned long long* __restrict__ pkey, unsigned long long* __restrict__ pfirst,
-                                        unsigned int* __restrict__ pcnt, const int* __restrict__ fin,
-                                        int* __restrict__ efinal) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_pairs) return;
-  if (x_first_inv(first2, c) == 0u) return;  // unclaimed
-  unsigned int first = ~x_first_inv(first2, c);
-  const long long i = x_rank_of(first >> 3, bits, prefix);
-  unsigned long long key = etab[slot_by_claim[c]].w1;
-  if (fin) pair_to_final(key, first, fin);
-  pkey[i] = key;
-  pfirst[i] = (unsigned long long)first;
-  if (efinal)
-    efinal[c] = (int)i;  // the occurrences are counted afterwards, per class id (bf_finish)
-  else
-    pcnt[i] = cnt_by_claim[c];
-}
-
-__global__ void k_x_sort_keys(const unsigned int* __restrict__ first2, long long n,
-                              unsigned int* __restrict__ keys, unsigned int* __restrict__ vals) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  keys[i] = ~x_first_inv(first2, i);
-  vals[i] = (unsigned int)i;
-}
-
-__global__ __launch_bounds__(256) void k_x_assign_nodes(
-    const unsigned int* __restrict__ first_sorted, const unsigned int* __restrict__ claim_sorted, long long n_nodes, int k,
-    int* __restrict__ final_of_claim, int* __restrict__ node_tokens, long long* __restrict__ node_first,
-    unsigned char* __restrict__ node_alive, const int* __restrict__ tokens, int flip) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned int first = 0u;
-  if (i < n_nodes) {
-    first = first_sorted[i];
-    final_of_claim[claim_sorted[i]] = (int)i;
-    node_first[i] = (long long)first;
-    node_alive[i] = 1;
-  }
-  node_tuples_from_reads(node_tokens, tokens, i < n_nodes ? (int)i : -1, first, k, flip);
-}
-
-// ------------------------------------------------------------------ components of a filtered build
-// The reference labels components once, in __init__, on the graph of ALL nodes (construct_graph.py:101-102,
-// :911-927) and keeps the labels through filter_graph.  A filtered build never makes the nodes and edges
-// below the threshold, so the labels are made in CLAIM space instead, from what the node pass left behind:
-// every window's claim (tok_slot) — two consecutive windows of a read are an edge of the unfiltered graph —
-// and every claim's first-seen value (saved by k_x_drop_claims).  Union-find over the claims; component id =
-// 1 + rank of the component's earliest first-seen among the components (= DFS discovery order over _nodes).
-__global__ void k_xc_init(int* parent, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) parent[i] = (int)i;
-}
-
-__global__ void k_xc_union(const int* __restrict__ tok_claim, long long n_tokens, int* parent) {
-  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t + 1 >= n_tokens) return;
-  const int raw = tok_claim[t];
-  if (raw == -1 || ((unsigned int)raw & AMG_LAST_FLAG)) return;
-  const int nxt = tok_claim[t + 1];
-  if (nxt == -1) return;
-  int a = (int)((unsigned int)raw & ~AMG_FLAG_MASK), b = (int)((unsigned int)nxt & ~AMG_FLAG_MASK);
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) break;
-    if (a > b) { int x = a; a = b; b = x; }
-    const int old = atomicCAS(parent + b, b, a);  // hook the larger root under the smaller
-    if (old == b) break;
-    b = old;
-  }
-}
-
-__global__ void k_xc_flatten(int* parent, long long n) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) parent[i] = uf_find(parent, (int)i);  // only thread i writes entry i; roots keep parent == self
-}
-
-__device__ __forceinline__ int xc_root(const int* __restrict__ parent, long long c) {
-  int r = parent[c];
-  while (parent[r] != r) r = parent[r];  // entries of non-roots may still name an intermediate ancestor
-  return r;
-}
-
-// best2[2 r] = the largest complemented first-seen (= the earliest) among the claims of root r; roots counted
-__global__ void k_xc_best(const int* __restrict__ parent, const unsigned int* __restrict__ first_all, long long n,
-                          unsigned int* __restrict__ best2, unsigned long long* __restrict__ n_roots) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  bool root = false;
-  if (c < n && first_all[c] != 0u) {
-    const int r = xc_root(parent, c);
-    root = r == (int)c;
-    atomicMax(best2 + 2ll * r, first_all[c]);
-  }
-  const unsigned long long m = __ballot(root);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_roots, (unsigned long long)__popcll(m));
-}
-
-__global__ void k_xc_label(const int* __restrict__ parent, const unsigned int* __restrict__ first_all, long long n,
-                           const unsigned int* __restrict__ best2, const unsigned int* __restrict__ bits,
-                           const long long* __restrict__ prefix, const int* __restrict__ final_of_claim,
-                           int* __restrict__ node_comp) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n || first_all[c] == 0u) return;
-  const int node = final_of_claim[c];
-  if (node < 0) return;  // the filter dropped this node
-  const unsigned int first = ~best2[2ll * xc_root(parent, c)];
-  node_comp[node] = (int)x_rank_of(first >> 1, bits, prefix) + 1;
-}
-
 // ------------------------------------------------------------------ edges, four adjacencies per thread
 // HOME = 0: a thread's four adjacencies are consecutive (one LDS read of its neighbours' words, one 16-byte store of its
 // results), every class lives where its key hashes to.
@@ -676,24 +436,6 @@ __global__ __launch_bounds__(TILE_THREADS, 8) void k_edges_v(
   }
 }
 
-// edge classes in first-seen order: key, first, count (counted per claim by k_count_ids)
-__global__ void k_x_gather_pairs(const unsigned int* __restrict__ first_sorted,
-                                 const unsigned int* __restrict__ claim_sorted, long long n_pairs,
-                                 const Slot16* __restrict__ etab, const unsigned int* __restrict__ slot_by_claim,
-                                 const unsigned int* __restrict__ cnt_by_claim,
-                                 unsigned long long* __restrict__ pkey, unsigned long long* __restrict__ pfirst,
-                                 unsigned int* __restrict__ pcnt, const int* __restrict__ fin) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_pairs) return;
-  const unsigned int c = claim_sorted[i];
-  unsigned long long key = etab[slot_by_claim[c]].w1;
-  unsigned int first = first_sorted[i];
-  if (fin) pair_to_final(key, first, fin);
-  pkey[i] = key;
-  pfirst[i] = (unsigned long long)first;
-  pcnt[i] = cnt_by_claim[c];
-}
-
 #define X_CTRS (F_SHARDS + 1)  // counters of a plain pass: F_SHARDS shards + the first tiles'
 
 // ------------------------------------------------------------------ host side
@@ -710,28 +452,6 @@ static long long head_tiles(const amg_ctx* c, long long n_tiles) {
   if (h > n_tiles / 16) h = n_tiles / 16;
   return h;
 }
-static const long long kRankBitmapMax = 16ll << 20;  // claims up to which the bitmap ranking is used (5.4 M: 0.38 vs 0.44 ms;
-                                                    // 0.5 M: 0.09 vs 0.16 ms); the radix sort beyond (AMG_X_RANK_SORT=1 forces it)
-
-// bitmap over the tokens (s1) with one bit per claim + exclusive prefix of the word popcounts (s5)
-static int x_rank_bitmap(amg_ctx* c, const unsigned int* first2, long long n, int shift) {
-  hipStream_t st = c->stream;
-  const long long words = (c->n_tokens >> 5) + 2;
-  AMGCHK(c->s1.ensure((size_t)words * sizeof(unsigned int)));
-  AMGCHK(c->s5.ensure((size_t)(words + 2) * sizeof(long long)));
-  AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
-  if (c->rank_flags_clean != words) {  // (else: zeroed behind the table pass's read-back, read_pass_status)
-    ClearList cl;
-    cl.add(c->s0.p, (size_t)words * 32);
-    AMGCHK(clear_many(c, cl));
-  }
-  c->rank_flags_clean = 0;
-  hipLaunchKernelGGL(k_x_rank_setflags, dim3(nblk(n, 256)), dim3(256), 0, st, first2, n, shift,
-                     c->s0.as<unsigned char>());
-  // the flag bytes are folded into the bitmap words by the scan that counts them (one launch, no count array)
-  return prim_exscan_flag_words(c, c->s0.as<unsigned char>(), c->s1.as<unsigned int>(), c->s5.as<long long>(), (size_t)words);
-}
-
 // claims from shard counters (XShard) for the inputs that get a head launch (4 M tokens and more: below that one
 // counter serves a pass's workgroups in the time the pass takes anyway); AMG_CLAIM_SHARDS = 0 / 1: never / always
 // (A/B + test switch)
@@ -757,7 +477,7 @@ static long long dense_tiles(long long head, long long n_tiles) {
 // The claim plan of one table pass (nodes or edge classes): where its claim ids come from and how many there can be.
 struct PassPlan {
   long long n_tiles;
-  bool plain;      // the caller is the plain build: counting / ranking follow the read-back directly, nobody else writes s0
+  bool rank_next;  // the caller ranks these claims before anybody else writes s0: the ranking's flag bytes are zeroed behind the read-back
   bool sharded;    // claims from the shard counters (then the ids in use have holes: space())
   unsigned int cap;          // claims per counter
   long long head;            // tiles of the head launch (0: none)
@@ -773,13 +493,12 @@ struct PassPlan {
     return s < (long long)max_claims ? s : (long long)max_claims;
   }
 };
-// sharded, rank_follows: as bx_nodes_upsert's; half: which half of f_ctrs (0 nodes, 1 edge classes)
-static int plan_pass(amg_ctx* c, long long n_tiles, long long claim_bound, bool sharded, bool rank_follows, int half,
-                     PassPlan* p) {
+// who: the table next to PassCaller (amg_internal.h); half: which half of f_ctrs (0 nodes, 1 edge classes)
+static int plan_pass(amg_ctx* c, long long n_tiles, long long claim_bound, PassCaller who, int half, PassPlan* p) {
+  const bool filtered_edges = who == PassCaller::FilteredBuild && half == 1;
   p->n_tiles = n_tiles;
-  p->plain = sharded && rank_follows;
-  c->rank_flags_clean = 0;
-  p->sharded = sharded && shard_claims(c, n_tiles);
+  p->rank_next = who != PassCaller::MergedLocal && !filtered_edges;
+  p->sharded = !filtered_edges && shard_claims(c, n_tiles);
   p->head = n_tiles > 0 ? head_tiles(c, n_tiles) : 0;
   p->cap = p->sharded ? shard_share(claim_bound) : (unsigned int)claim_bound;
   p->head_cap = p->sharded ? dense_tiles(p->head, n_tiles) * TILE : 0;
@@ -809,23 +528,21 @@ static void launch_head_and_main(amg_ctx* c, const PassPlan& p, const char* name
 }
 
 // the status words after a table pass: with shard counters (p.ctrs) their sum replaces host[count_word], the fullest
-// shard's count goes to *most.  p.plain: the flag bytes of the ranking bitmap that follows (x_rank_bitmap) are zeroed
-// behind the read-back kernel, while the host waits
+// shard's count goes to *most.  p.rank_next: the flag bytes of the ranking that follows are zeroed behind the read-back
+// kernel, while the host waits, and *zeroed says so
 static int read_pass_status(amg_ctx* c, const PassPlan& p, int count_word,
-                            unsigned long long* host /*[ST_WORDS + X_CTRS]*/, unsigned long long* most) {
+                            unsigned long long* host /*[ST_WORDS + X_CTRS]*/, unsigned long long* most,
+                            RankFlagsZeroed* zeroed) {
   FetchList l;
   l.add_words(c->status.p, ST_WORDS);
   if (p.ctrs)
     for (int i = 0; i < X_CTRS; ++i) l.add(p.ctrs + (size_t)i * F_CTR_STRIDE);
   unsigned long long* v = host;
   ClearList fill;
-  const long long words = (c->n_tokens >> 5) + 2;
-  if (p.plain) {
-    AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
-    fill.add(c->s0.p, (size_t)words * 32);
-  }
-  AMGCHK(fetch(c, l, v, p.plain ? &fill : nullptr));
-  if (p.plain) c->rank_flags_clean = words;
+  RankFlagsZeroed z;
+  if (p.rank_next) AMGCHK(rank_flags_zero_behind(c, &fill, &z));
+  AMGCHK(fetch(c, l, v, p.rank_next ? &fill : nullptr));
+  if (zeroed) *zeroed = z;
   *most = 0;
   if (p.ctrs) {
     unsigned long long sum = 0;
@@ -840,15 +557,10 @@ static int read_pass_status(amg_ctx* c, const PassPlan& p, int count_word,
 
 // bits per token of the packed tuple: 16 whenever that fits (constant shifts in the kernels); AMG_X_TIGHT_BITS=1:
 // as few as the vocabulary needs (test switch: the kernels' general packing, which large vocabularies take)
-int bx_bits(const amg_ctx* c, int k) {
+static int bx_bits(const amg_ctx* c, int k) {
   const int need = ilog2_ceil((uint64_t)(c->two_v > 2 ? c->two_v : 2));
   if (need <= 16 && (long long)k * 16 <= 94 && !c->sw.tight_bits) return 16;
   return need;
-}
-
-bool bx_applicable(const amg_ctx* c, int k) {
-  if (c->dist_mode || c->count_inline) return false;
-  return bx_fits(c, k);
 }
 
 // 16-byte slots may be used: 32-bit first-seen ((token << 3) | orientation, per shard in a merged build), no AMG_KEY_MODE=fp
@@ -860,14 +572,13 @@ bool bx_tuple_fits(const amg_ctx* c, int k) {
 }
 
 // the 16-byte-slot build applies: the tuple fits, or it does not and its 94-bit fingerprint is the key (x_fp94)
-bool bx_fits(const amg_ctx* c, int k) {
+static bool bx_fits(const amg_ctx* c, int k) {
   return bx_tuple_fits(c, k) || (x_slots_allowed(c) && (long long)k * bx_bits(c, k) > 94);
 }
 
-// windows -> node table, claim ids, node ids, node arrays.  AMG_E_OVERFLOW + *which = OV_NODE_TABLE: table full
-int bx_nodes(amg_ctx* c, int k, Overflow* which) {
-  AMGCHK(bx_nodes_upsert(c, k, which, true));
-  return bx_nodes_rank(c);
+bool bx_applicable(const amg_ctx* c, int k) {
+  if (c->dist_mode || c->count_inline) return false;
+  return bx_fits(c, k);
 }
 
 // The compile-time node kernels, ONE table for k_nodes_m and k_nodes_v: (b16, k in {3, 5, 7}, two) -> <TWO, K, B16>
@@ -878,10 +589,10 @@ int bx_nodes(amg_ctx* c, int k, Overflow* which) {
    : (k) == 5          ? ((two) ? KERN<true, 5, false, HEAD> : KERN<false, 5, false, HEAD>)     \
                        : ((two) ? KERN<true, 7, false, HEAD> : KERN<false, 7, false, HEAD>))
 
-// the table pass alone: claims 0 .. n_local_nodes-1 with their first-seen / slot arrays
-// sharded: claim ids may come from shard counters (then x_nspace > n_nodes: ids nobody took in between)
-// rank_follows: the caller ranks the claims next (x_rank_bitmap): its flag bytes are zeroed behind the status read-back
-int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded, bool rank_follows) {
+// the table pass alone: claims 0 .. n_local_nodes-1 with their first-seen / slot arrays (with shard counters
+// x_nspace > n_nodes: ids nobody took in between).  AMG_E_OVERFLOW + *which = OV_NODE_TABLE: table full.
+// *zeroed (nullptr: not wanted): what the ranking of these claims may take for granted
+int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, PassCaller who, RankFlagsZeroed* zeroed) {
   *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens;
@@ -900,7 +611,7 @@ int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded, bool rank_
   const size_t home_n = buckets ? (size_t)4 * (size_t)c->two_v : 0;  // 8 slots x (two_v / 2) gene ranks
   const size_t tab_slots = (size_t)c->node_slots + home_n;
   PassPlan p;
-  AMGCHK(plan_pass(c, n_tiles, ((long long)tab_slots < T ? (long long)tab_slots : T) + 1, sharded, rank_follows, 0, &p));
+  AMGCHK(plan_pass(c, n_tiles, ((long long)tab_slots < T ? (long long)tab_slots : T) + 1, who, 0, &p));
   // ---- ensure
   AMGCHK(c->tok_slot.ensure((size_t)(T + 8) * sizeof(int)));
   AMGCHK(c->tok_node.ensure((size_t)(T + 8) * sizeof(int)));
@@ -961,7 +672,7 @@ int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded, bool rank_
   }
   // ---- read back, decode
   unsigned long long hs[ST_WORDS + X_CTRS], most;
-  AMGCHK(read_pass_status(c, p, ST_NODE_INSERTS, hs, &most));
+  AMGCHK(read_pass_status(c, p, ST_NODE_INSERTS, hs, &most, zeroed));
   if (hs[ST_BADINPUT])
     return amg_fail(AMG_E_ARG, hs[ST_BADINPUT] == 1 ? "read_offsets must start at 0, never decrease and end at the token count"
                                                     : "a token lies outside [0, two_v)");
@@ -974,130 +685,13 @@ int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded, bool rank_
   c->n_short = (int64_t)hs[ST_N_SHORT];
   c->n_local_nodes = c->n_nodes = (int64_t)hs[ST_NODE_INSERTS];
   c->x_nspace = p.space(c->n_nodes, most);
-  c->x_max_claims = (int64_t)p.max_claims;
-  return AMG_OK;
-}
-
-// node table pass, then only the nodes with coverage >= min_cov are kept: ids, arrays and coverages of the
-// survivors; x_final = -2 for the others
-int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, Overflow* which) {
-  hipStream_t st = c->stream;
-  c->filtered_build = true;
-  const int r0 = bx_nodes_upsert(c, k, which, true);
-  c->filtered_build = false;
-  AMGCHK(r0);
-  // claim ids in use lie below n (shard counters: with ids nobody took in between — first-seen 0, like the claims
-  // dropped here)
-  const long long n = c->x_nspace, T = c->n_tokens;
-  stage_begin(c, "node_count");  // per claim, straight from the per-window claims (construct_node.py:33-36)
-  AMGCHK(c->x_ecnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, CountNodes, IdsClaimsMarked, c->tok_slot.as<int>(), T, n, c->x_ecnt.as<unsigned int>()));
-  stage_end(c);
-  stage_begin(c, "node_filter");
-  AMGCHK(c->x_first_all.ensure((size_t)(n + 2) * sizeof(unsigned int)));
-  c->comp_from_claims = true;
-  unsigned long long* kept = c->status.as<unsigned long long>() + ST_COMPACT_A;
-  HIPCHK(hipMemsetAsync(kept, 0, sizeof(unsigned long long), st));
-  if (n > 0)
-    hipLaunchKernelGGL(k_x_drop_claims, dim3(nblk(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), n,
-                       min_cov, c->x_first.as<unsigned int>(), c->x_final.as<int>(), kept,
-                       c->x_first_all.as<unsigned int>());
-  unsigned long long D = 0;
-  {
-    FetchList l;
-    l.add(kept);
-    l.add(c->status.as<unsigned long long>() + ST_COLLISION);
-    unsigned long long v[2] = {0, 0};
-    AMGCHK(fetch(c, l, v));
-    D = v[0];
-    if (v[1]) {  // two gene-mers share a fingerprint (k_x_verify_fp): the build is repeated with the next seed
-      stage_end(c);
-      return overflowed(which, OV_COLLISION);
-    }
-  }
-  stage_end(c);
-  c->n_nodes = (int64_t)D;
-  AMGCHK(bx_nodes_rank(c));
-  if (n > 0 && D > 0)
-    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(nblk(n, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(),
-                       c->x_first.as<unsigned int>(), c->x_final.as<int>(), n, c->node_cov.as<unsigned int>(), (int*)nullptr);
-  return AMG_OK;
-}
-
-// node id = rank of first-seen among the claims; node arrays
-int bx_nodes_rank(amg_ctx* c) {
-  hipStream_t st = c->stream;
-  const long long T = c->n_tokens;
-  const int k = c->k;
-  stage_begin(c, "node_rank");
-  const long long D = c->n_nodes;
-  AMGCHK(c->s1.ensure((size_t)(D + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s2.ensure((size_t)(D + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s3.ensure((size_t)(D + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s4.ensure((size_t)(D + 1) * sizeof(unsigned int)));
-  AMGCHK(bs_alloc_nodes(c, D));
-  const long long S = c->x_nspace;  // claim ids in use (== D unless handed out in interleaved shards)
-  if (D > 0 && ((D <= kRankBitmapMax && !c->sw.rank_sort) || S != D)) {
-    AMGCHK(x_rank_bitmap(c, c->x_first.as<unsigned int>(), S, 1));
-    hipLaunchKernelGGL(k_x_assign_nodes_ranked, dim3(nblk(S, 256)), dim3(256), 0, st,
-                       c->x_first.as<unsigned int>(), S,
-                       c->s1.as<unsigned int>(), c->s5.as<long long>(), k, c->x_final.as<int>(), c->node_tokens.as<int>(),
-                       c->node_first.as<long long>(), c->node_alive.as<unsigned char>(), c->tokens.as<int>(), c->two_v - 1);
-  } else if (D > 0) {
-    c->rank_flags_clean = 0;  // (s0 is about to be reused by whoever comes next: nothing of it is known to be zero)
-    hipLaunchKernelGGL(k_x_sort_keys, dim3(nblk(D, 256)), dim3(256), 0, st, c->x_first.as<unsigned int>(),
-                       D, c->s1.as<unsigned int>(),
-                       c->s3.as<unsigned int>());
-    AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s2.as<unsigned int>(), c->s3.as<unsigned int>(),
-                             c->s4.as<unsigned int>(), (size_t)D, ilog2_ceil((uint64_t)T * 2 + 2) + 1));
-    hipLaunchKernelGGL(k_x_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
-                       c->s4.as<unsigned int>(), D, k, c->x_final.as<int>(),
-                       c->node_tokens.as<int>(), c->node_first.as<long long>(), c->node_alive.as<unsigned char>(),
-                       c->tokens.as<int>(), c->two_v - 1);
-  }
-  stage_end(c);
-  return AMG_OK;
-}
-
-// adjacencies -> edge-class table, claims, pair arrays in first-seen order, coverages.
-// AMG_E_OVERFLOW + *which = OV_EDGE_TABLE: edge table full
-int bx_edges(amg_ctx* c, Overflow* which, unsigned int min_edge_cov) {
-  // a plain build counts its nodes BEFORE the edge pass: the nodes of coverage 1 (nine in ten of an uncorrected
-  // graph) mark the edge classes that occur once, and those need no table (k_edges_v<.., LONE>)
-  bool lone = false;
-  if (min_edge_cov == 0) {
-    const bool can = c->sw.edge_home && c->n_nodes > 0;
-    // AMG_EDGE_LONE (A/B + test switch): 0 never, 1 whenever the kernel allows it; else where it is
-    // worth its extra words per window: where many nodes are single, more than one node per 16 windows
-    lone = can && (c->sw.edge_lone >= 0 ? c->sw.edge_lone != 0 : c->n_nodes * 16 > c->n_tokens);
-    AMGCHK(bx_node_count(c, lone));
-  }
-  AMGCHK(bx_edges_upsert(c, which, lone, min_edge_cov == 0));
-  return bx_edges_rank(c, min_edge_cov, min_edge_cov == 0);
-}
-
-// node coverage of a plain build (construct_node.py:33-36): occurrences per CLAIM from the node pass's per-window
-// claims — the occurrence that created a key is marked there, so the keys seen once (most of an uncorrected graph)
-// cost nothing — then one store per claim into the node's counter.  tag: x_ftag = x_final with AMG_SINGLE_BIT
-int bx_node_count(amg_ctx* c, bool tag) {
-  const long long T = c->n_tokens, D = c->n_nodes;
-  stage_begin(c, "node_count");
-  const long long S = c->x_nspace;
-  AMGCHK(c->x_ncnt.ensure((size_t)(S + 2) * sizeof(unsigned int)));
-  if (tag) AMGCHK(c->x_ftag.ensure((size_t)(S + 2) * sizeof(int)));
-  AMGCHK(count_ids(c, CountNodes, IdsClaimsMarked, c->tok_slot.as<int>(), T, S, c->x_ncnt.as<unsigned int>()));
-  if (S > 0 && D > 0)
-    hipLaunchKernelGGL(k_x_cov_from_claims, dim3(nblk(S, 256)), dim3(256), 0, c->stream,
-                       c->x_ncnt.as<unsigned int>(), c->x_first.as<unsigned int>(), c->x_final.as<int>(), S,
-                       c->node_cov.as<unsigned int>(), tag ? c->x_ftag.as<int>() : (int*)nullptr);
-  stage_end(c);
   return AMG_OK;
 }
 
 // the table pass alone: tok_node from x_final, edge-class claims 0 .. n_local_pairs-1
 // lone: x_ftag marks the nodes of coverage 1 (bx_node_count); their classes bypass the table
-// sharded, rank_follows: as bx_nodes_upsert's
-int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, bool sharded, bool rank_follows) {
+// who, zeroed: as bx_nodes_upsert's.  AMG_E_OVERFLOW + *which = OV_EDGE_TABLE: edge table full
+int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, PassCaller who, RankFlagsZeroed* zeroed) {
   *which = OV_NONE;
   hipStream_t st = c->stream;
   const long long T = c->n_tokens, D = c->n_nodes;
@@ -1113,7 +707,7 @@ int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, bool sharded, bool r
   // claims: at most one per table slot, plus (lone) two classes per single node, never more than the windows
   const long long claim_bound = (long long)tab_slots + (lone ? 2 * D : 0);
   PassPlan p;
-  AMGCHK(plan_pass(c, n_tiles, (claim_bound < T ? claim_bound : T) + 1, sharded, rank_follows, 1, &p));
+  AMGCHK(plan_pass(c, n_tiles, (claim_bound < T ? claim_bound : T) + 1, who, 1, &p));
   // ---- ensure
   AMGCHK(c->tok_pair.ensure((size_t)(T + 8) * sizeof(int)));
   AMGCHK(c->edge_tab.ensure((tab_slots + (lone ? p.max_claims : 0)) * sizeof(Slot16)));  // (lone classes: slot = tab_slots + claim)
@@ -1145,120 +739,11 @@ int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, bool sharded, bool r
   });
   // ---- read back, decode
   unsigned long long hs[ST_WORDS + X_CTRS], most;
-  AMGCHK(read_pass_status(c, p, ST_PAIR_INSERTS, hs, &most));
+  AMGCHK(read_pass_status(c, p, ST_PAIR_INSERTS, hs, &most, zeroed));
   if (hs[ST_MISC]) return amg_fail(AMG_E_HIP, "edge pass: a claim id was never published");
   if (hs[ST_COLLISION]) return overflowed(which, OV_COLLISION);  // (fingerprint keys: k_x_verify_fp found two gene-mers under one key)
   if (hs[ST_OVERFLOW]) return overflowed(which, OV_EDGE_TABLE);
   c->n_local_pairs = c->n_pairs = (int64_t)hs[ST_PAIR_INSERTS];
   c->x_espace = p.space(c->n_pairs, most);
-  c->x_max_eclaims = (int64_t)p.max_claims;
-  return AMG_OK;
-}
-
-// coverages, edge classes in first-seen order.  min_edge_cov > 0: the build applies the coverage filter on the
-// way (bx_nodes_filtered has the node coverages already; classes below min_edge_cov are dropped before ranking)
-int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov, bool nodes_counted) {
-  const long long T = c->n_tokens, P = c->x_espace;  // (claim ids in use lie below P)
-  if (min_edge_cov == 0 && !nodes_counted) AMGCHK(bx_node_count(c, false));
-  // edge-class coverage per claim
-  stage_begin(c, "edge_count");
-  AMGCHK(c->x_ecnt.ensure((size_t)(P + 2) * sizeof(unsigned int)));
-  AMGCHK(count_ids(c, CountEdgeClasses, IdsClaimsMarked, c->tok_pair.as<int>(), T, P, c->x_ecnt.as<unsigned int>()));
-  stage_end(c);
-  if (min_edge_cov > 1 && P > 0) {  // filter_graph's edge threshold (:531-535)
-    hipStream_t st = c->stream;
-    unsigned long long* kept = c->status.as<unsigned long long>() + ST_COMPACT_A;
-    HIPCHK(hipMemsetAsync(kept, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_x_drop_claims, dim3(nblk(P, 256)), dim3(256), 0, st, c->x_ecnt.as<unsigned int>(), P,
-                       min_edge_cov, c->x_efirst.as<unsigned int>(), (int*)nullptr, kept, (unsigned int*)nullptr);
-    unsigned long long left = 0;
-    FetchList l;
-    l.add(kept);
-    AMGCHK(fetch(c, l, &left));
-    c->n_pairs = (int64_t)left;  // x_espace stays: the dropped classes are holes of the claim space
-  }
-  return bx_pairs_rank(c, nullptr, nullptr);
-}
-
-// after bs_finish_from_pairs of a filtered build: the reads the filter touched
-int bx_flag_dead_reads(amg_ctx* c) {
-  if (c->n_reads > 0)
-    hipLaunchKernelGGL(k_x_flag_dead_reads, dim3(nblk(c->n_reads, FD_READS)), dim3(256), 0, c->stream,
-                       c->tok_node.as<int>(), c->read_off.as<long long>(), c->n_reads, c->read_fix.as<unsigned char>());
-  return AMG_OK;
-}
-
-// edge classes in first-seen order (pair_key / pair_first / pair_cnt) from the claims' arrays;
-// final_of_claim != nullptr: the classes are keyed by node CLAIM ids (fused table pass)
-// efinal != nullptr: class id per claim is written there and pair_cnt is left to the caller
-int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal) {
-  hipStream_t st = c->stream;
-  const long long T = c->n_tokens, P = c->n_pairs;
-  stage_begin(c, "edge_rank");
-  AMGCHK(bs_alloc_pairs(c, P));
-  AMGCHK(c->s1.ensure((size_t)(P + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s2.ensure((size_t)(P + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s3.ensure((size_t)(P + 1) * sizeof(unsigned int)));
-  AMGCHK(c->s4.ensure((size_t)(P + 1) * sizeof(unsigned int)));
-  const long long S = c->x_espace;
-  if (P > 0 && ((P <= kRankBitmapMax && !c->sw.rank_sort) || S != P || efinal)) {
-    AMGCHK(x_rank_bitmap(c, c->x_efirst.as<unsigned int>(), S, 3));
-    hipLaunchKernelGGL(k_x_gather_pairs_ranked, dim3(nblk(S, 256)), dim3(256), 0, st,
-                       c->x_efirst.as<unsigned int>(), S,
-                       c->s1.as<unsigned int>(), c->s5.as<long long>(), c->edge_tab.as<Slot16>(),
-                       c->x_eslot.as<unsigned int>(), c->x_ecnt.as<unsigned int>(),
-                       c->pair_key.as<unsigned long long>(), c->pair_first.as<unsigned long long>(),
-                       c->pair_cnt.as<unsigned int>(), final_of_claim, efinal);
-  } else if (P > 0) {
-    c->rank_flags_clean = 0;
-    if (efinal) return amg_fail(AMG_E_STATE, "bx_pairs_rank: class ids per claim need the bitmap ranking");
-    hipLaunchKernelGGL(k_x_sort_keys, dim3(nblk(P, 256)), dim3(256), 0, st, c->x_efirst.as<unsigned int>(),
-                       P, c->s1.as<unsigned int>(),
-                       c->s3.as<unsigned int>());
-    AMGCHK(prim_sort_u32_u32(c, c->s1.as<unsigned int>(), c->s2.as<unsigned int>(), c->s3.as<unsigned int>(),
-                             c->s4.as<unsigned int>(), (size_t)P, ilog2_ceil((uint64_t)T * 8 + 8) + 1));
-    hipLaunchKernelGGL(k_x_gather_pairs, dim3(nblk(P, 256)), dim3(256), 0, st, c->s2.as<unsigned int>(),
-                       c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot16>(), c->x_eslot.as<unsigned int>(),
-                       c->x_ecnt.as<unsigned int>(), c->pair_key.as<unsigned long long>(),
-                       c->pair_first.as<unsigned long long>(), c->pair_cnt.as<unsigned int>(), final_of_claim);
-  }
-  stage_end(c);
-  return AMG_OK;
-}
-
-// component ids of a filtered build (see k_xc_*)
-int bx_components_from_claims(amg_ctx* c) {
-  hipStream_t st = c->stream;
-  const long long S = c->x_nspace, T = c->n_tokens, D = c->n_nodes;
-  stage_begin(c, "components");
-  AMGCHK(c->node_comp.ensure((size_t)(D + 1) * sizeof(int)));
-  AMGCHK(c->s3.ensure((size_t)(S + 2) * sizeof(int)));
-  AMGCHK(c->s4.ensure((size_t)(2 * S + 4) * sizeof(unsigned int)));
-  int* parent = c->s3.as<int>();
-  unsigned int* best2 = c->s4.as<unsigned int>();
-  unsigned long long* n_roots = c->status.as<unsigned long long>() + ST_COMPACT_A;
-  long long ncomp = 0;
-  if (S > 0) {
-    ClearList cl;
-    cl.add(best2, (size_t)(2 * S + 2) * sizeof(unsigned int));
-    cl.add(n_roots, sizeof(unsigned long long));
-    AMGCHK(clear_many(c, cl));
-    hipLaunchKernelGGL(k_xc_init, dim3(nblk(S, 256)), dim3(256), 0, st, parent, S);
-    if (T > 1)
-      hipLaunchKernelGGL(k_xc_union, dim3(nblk(T, 256)), dim3(256), 0, st, c->tok_slot.as<int>(), T, parent);
-    hipLaunchKernelGGL(k_xc_flatten, dim3(nblk(S, 256)), dim3(256), 0, st, parent, S);
-    hipLaunchKernelGGL(k_xc_best, dim3(nblk(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
-                       best2, n_roots);
-    AMGCHK(x_rank_bitmap(c, best2, S, 1));  // non-roots keep {0, 0}: skipped like unclaimed ids
-    hipLaunchKernelGGL(k_xc_label, dim3(nblk(S, 256)), dim3(256), 0, st, parent, c->x_first_all.as<unsigned int>(), S,
-                       best2, c->s1.as<unsigned int>(), c->s5.as<long long>(), c->x_final.as<int>(),
-                       c->node_comp.as<int>());
-    FetchList l;
-    l.add(n_roots);
-    AMGCHK(fetch(c, l, reinterpret_cast<unsigned long long*>(&ncomp)));
-  }
-  stage_end(c);
-  c->n_components = ncomp;
-  c->comp_valid = true;
   return AMG_OK;
 }

@@ -295,7 +295,6 @@ int derive_commit(amg_ctx* c, long long D2, long long P2) {
   c->n_nodes = c->n_local_nodes = D2;
   c->n_pairs = c->n_local_pairs = P2;
   c->comp_from_claims = false;  // (labels of the graph as it is now, made when somebody asks)
-  c->filtered_build = false;
   AMGCHK(bs_finish_from_pairs(c));
   c->built = true;
   c->derived = true;

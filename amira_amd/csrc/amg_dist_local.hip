@@ -272,7 +272,7 @@ static int nodes_local_x(amg_ctx* c, DistState* d, unsigned long long key_mask) 
   const int k = d->k, world = d->world;
   Overflow which;
   AMGCHK(pass_until_fits(c, OV_NODE_TABLE, &which,
-                         [&](Overflow* w) { return bx_nodes_upsert(c, k, w, true, false); }));  // (claims from the shard counters)
+                         [&](Overflow* w) { return bx_nodes_upsert(c, k, w, PassCaller::MergedLocal, nullptr); }));
   // claim ids in use lie below n (shard counters: with ids nobody took in between, first-seen 0)
   const long long n = c->x_nspace, T = c->n_tokens;
   // local occurrence counts per claim, straight from the per-window claims
@@ -299,7 +299,9 @@ static int edges_local_x(amg_ctx* c, DistState* d) {
   hipStream_t st = c->stream;
   const int world = d->world;
   Overflow which;
-  const int fits = pass_until_fits(c, OV_EDGE_TABLE, &which, [&](Overflow* w) { return bx_edges_upsert(c, w, false, true, false); });
+  const int fits = pass_until_fits(c, OV_EDGE_TABLE, &which, [&](Overflow* w) {
+    return bx_edges_upsert(c, w, false, PassCaller::MergedLocal, nullptr);
+  });
   AMGCHK(edge_pass_result(fits, which, "two gene-mers share a merge key"));
   const long long n = c->x_espace, T = c->n_tokens;  // (claim ids in use lie below n: see nodes_local_x)
   stage_begin(c, "edge_count");

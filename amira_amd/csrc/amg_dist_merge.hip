@@ -136,12 +136,6 @@ int reduce_records(amg_ctx* c, DistState* d, int is_edge) {
 }
 
 // ------------------------------------------------------------------ phase: hold
-__device__ __forceinline__ long long d_rank_of(unsigned long long t, const unsigned int* __restrict__ bits,
-                                               const long long* __restrict__ prefix) {
-  const unsigned int w = bits[t >> 5];
-  return prefix[t >> 5] + (long long)__popc(w & ((1u << (t & 31)) - 1u));
-}
-
 // exact-key shards: one flag byte per LOCAL token at the first-seen position of every claim this rank holds
 __global__ void k_xh_flags(const unsigned long long* __restrict__ replies, long long n, const unsigned int* __restrict__ order,
                            const unsigned int* __restrict__ first2, unsigned long long base, int shift,
@@ -168,7 +162,7 @@ __global__ void k_xh_emit_nodes(const unsigned long long* __restrict__ replies, 
   const unsigned int c = order ? order[j] : (unsigned int)j;
   const unsigned int local = ~x_first_inv(first2, c);
   if (base + (unsigned long long)local != g) return;
-  unsigned int* w = out + (size_t)d_rank_of(local >> 1, bits, prefix) * rec_words;
+  unsigned int* w = out + (size_t)x_rank_of(local >> 1, bits, prefix) * rec_words;
   held_put_node_head(w, g, replies[2 * j + 1]);
   const Slot16 s = tab[slot_by_claim[c]];
   const unsigned int tag = x_tag_of(s, two);
@@ -189,7 +183,7 @@ __global__ void k_xh_emit_edges(const unsigned long long* __restrict__ replies, 
   const unsigned int c = order ? order[j] : (unsigned int)j;
   const unsigned int local = ~x_first_inv(first2, c);
   if (base + (unsigned long long)local != g) return;
-  unsigned int* w = out + 5 * d_rank_of(local >> 3, bits, prefix);
+  unsigned int* w = out + 5 * x_rank_of(local >> 3, bits, prefix);
   const unsigned long long key = sent[3 * j];
   held_put_edge(w, key, g, replies[2 * j + 1]);
 }
@@ -250,7 +244,7 @@ __global__ void k_hc_msg(const long long* __restrict__ n_held, int attempt, cons
 // holders ranked, held records emitted in local first-seen order, the number held in d->hc_send
 int hold_records(amg_ctx* c, DistState* d, int is_edge) {
   hipStream_t st = c->stream;
-  const long long n = d->n_send, T = c->n_tokens;
+  const long long n = d->n_send;
   const unsigned long long* rep = static_cast<const unsigned long long*>(d->rep_in_p);
   const unsigned int* order = send_order(d);
   const int shift = is_edge ? 3 : 1;
@@ -259,31 +253,22 @@ int hold_records(amg_ctx* c, DistState* d, int is_edge) {
   unsigned long long* status = c->status.as<unsigned long long>();
   const long long* n_held = nullptr;
   if (c->dist_x) {
-    const long long words = (T >> 5) + 2;
-    AMGCHK(c->s0.ensure((size_t)words * 32 + 64));
-    AMGCHK(c->s1.ensure((size_t)words * sizeof(unsigned int)));
-    AMGCHK(c->s5.ensure((size_t)(words + 2) * sizeof(long long)));
-    c->rank_flags_clean = 0;
-    {
-      ClearList cl;
-      cl.add(c->s0.p, (size_t)words * 32);
-      AMGCHK(clear_many(c, cl));
-    }
+    unsigned char* flags;
+    RankBitmap r;
+    AMGCHK(rank_bitmap_begin(c, RankFlagsZeroed{}, &flags));
     const unsigned int* first2 = is_edge ? c->x_efirst.as<unsigned int>() : c->x_first.as<unsigned int>();
     if (n > 0)
-      hipLaunchKernelGGL(k_xh_flags, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base, shift,
-                         c->s0.as<unsigned char>());
-    AMGCHK(prim_exscan_flag_words(c, c->s0.as<unsigned char>(), c->s1.as<unsigned int>(), c->s5.as<long long>(), (size_t)words));
+      hipLaunchKernelGGL(k_xh_flags, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base, shift, flags);
+    AMGCHK(rank_bitmap_finish(c, &r));
     if (n > 0 && !is_edge)
       hipLaunchKernelGGL(k_xh_emit_nodes, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base,
-                         c->s1.as<unsigned int>(), c->s5.as<long long>(), c->node_tab.as<Slot16>(),
+                         r.bits, r.prefix, c->node_tab.as<Slot16>(),
                          c->x_slot.as<unsigned int>(), c->k, c->x_bits, c->x_two ? 1 : 0,
                          d->held.as<unsigned int>(), rb / 4, held_tok16(c->two_v) ? 1 : 0);
     else if (n > 0)
       hipLaunchKernelGGL(k_xh_emit_edges, dim3(nblk(n, 256)), dim3(256), 0, st, rep, n, order, first2, base,
-                         c->s1.as<unsigned int>(), c->s5.as<long long>(), d->send.as<unsigned long long>(),
-                         d->held.as<unsigned int>());
-    n_held = c->s5.as<long long>() + words;
+                         r.bits, r.prefix, d->send.as<unsigned long long>(), d->held.as<unsigned int>());
+    n_held = r.total;
   } else {
     AMGCHK(c->s4.ensure((size_t)(n + 2) * sizeof(unsigned int)));
     AMGCHK(c->s5.ensure((size_t)(n + 2) * sizeof(long long)));

@@ -132,7 +132,6 @@ struct BuildSwitches {
   bool key_fp = false;          // AMG_KEY_MODE=fp: the 32-byte fingerprint path of amg_build_fp.hip
   bool node_buckets = true;     // AMG_NODE_BUCKETS=0: hashed node slots only (k_nodes_v)
   bool generic_k = false;       // AMG_X_GENERIC_K: the node kernel with k at run time for every k
-  bool rank_sort = false;       // AMG_X_RANK_SORT: radix sort instead of the bitmap ranking where both apply
   int edge_lone = -1;           // AMG_EDGE_LONE: 0 never, 1 whenever the kernel allows it, -1 (unset) by the node count
   bool edge_home = true;        // AMG_EDGE_HOME=0: no home slots in the edge table
   bool no_derive = false;       // AMG_NO_DERIVE: never derive the rebuild from the graph at hand
@@ -194,14 +193,13 @@ struct amg_ctx {
   int c_node_bound_k = 0;
   int64_t hint_bound = 0;    // amg_set_reads_from_corrected: the source's bound for THESE reads, applied by a build at hint_bound_k
   int hint_bound_k = 0;
-  bool filtered_build = false;  // bx_nodes_upsert is running for amg_build_filtered (head launch: see there)
   int64_t n_local_nodes = 0, n_local_pairs = 0;  // before a multi-GPU merge
   int64_t tok_base = 0;   // global index of this shard's first token (0 on a single GPU)
   int64_t tok_total = 0;  // tokens over all shards
 
   DevBuf node_tab;   // Slot[node_slots]
   DevBuf edge_tab;   // Slot[edge_slots]
-  DevBuf tok_slot;   // int32[n_tokens]  slot index | LAST flag, -1 = no window
+  DevBuf tok_slot;   // int32[n_tokens]  exact keys: claim id | LAST / MADE flags (claim_word); 32-byte path: slot index | LAST flag; -1 = no window
   DevBuf tok_node;   // int32[n_tokens]  node id, -1 no window, -2 removed
   DevBuf tok_dir;    // int8 [n_tokens]
   DevBuf tok_pair;   // int32[n_tokens]  edge-class slot (then id) of the adjacency t -> t+1
@@ -261,17 +259,14 @@ struct amg_ctx {
   int x_kbits = 0;           // x_bits as the kernels take it: 0 for fingerprint keys
   int64_t x_nspace = 0, x_espace = 0;  // claim ids in use are below these (== n_nodes / n_pairs unless the
                                        // claims came from the shard counters: XShard in amg_x.h)
-  int64_t x_max_claims = 0, x_max_eclaims = 0;  // capacity of the per-claim arrays (second half of x_first / x_efirst starts there)
   bool dist_x = false;       // this merged build keeps its LOCAL tables in the exact-key layout
   DevBuf x_first, x_slot;    // uint32[claims]  ~first_seen of a node claim, its table slot
   DevBuf x_final;            // int32 [claims]  claim id -> node id
   DevBuf x_efirst, x_eslot;  // the same for edge-class claims
   DevBuf x_ecnt;             // uint32[edge claims] occurrences
   DevBuf x_ncnt;             // uint32[node claims] occurrences (plain build: scattered into node_cov)
-  int64_t rank_flags_clean = 0;  // words of the ranking bitmap's flag bytes (s0) a read-back's filler has zeroed already
   DevBuf x_ftag;             // int32 [node claims] x_final | AMG_SINGLE_BIT on nodes of coverage 1 (edge pass with lone classes)
-  DevBuf f_ctrs;             // fused table pass: per-shard claim counters
-  DevBuf x_efinal;           // int32 [edge claims] claim id -> edge-class id
+  DevBuf f_ctrs;             // uint64[2 halves x X_CTRS counters, F_CTR_STRIDE words apart] claim counters of the node / edge-class pass (plan_pass)
   DevBuf x_first_all;        // uint32[claims] filtered build: ~first_seen of EVERY claim (k_x_drop_claims zeroes x_first)
   bool comp_from_claims = false;  // filtered build: component ids come from the claims (bx_components_from_claims)
 
@@ -472,22 +467,44 @@ int count_ids(amg_ctx* c, CountKind what, CountIds form, int* ids, long long n, 
 #define COUNT_LEARN_WORDS 8  // done flags that count_learn_add asks for
 bool count_learn_add(amg_ctx* c, FetchList* l);
 void count_learn_take(amg_ctx* c, const unsigned long long* done /*[COUNT_LEARN_WORDS]*/);
-// the exact-key path (amg_build_x.hip)
+// the exact-key path.  Who runs a table pass decides where its claim ids come from and whether the flag bytes of the ranking
+// that follows are zeroed behind the pass's status read-back (plan_pass):
+//                                            shard counters                 flag bytes zeroed behind the read-back
+//   PlainBuild     bx_nodes, bx_edges        by size (shard_claims)         yes
+//   FilteredBuild  bx_nodes_filtered         by size                        yes
+//                  bx_edges                  never                          no
+//   MergedLocal    amg_dist_local.hip        by size                        no (the merge ranks after its exchanges)
+enum class PassCaller { PlainBuild, FilteredBuild, MergedLocal };
+// Proof that the flag bytes of the bitmap ranking are zero: made where they were zeroed (rank_flags_zero_behind), handed
+// to the ranking that uses them up.  The default proves nothing and costs the ranking one clear.
+struct RankFlagsZeroed {
+  const void* flags = nullptr;
+  long long words = 0;
+};
+// table passes (amg_build_x.hip)
 bool bx_applicable(const amg_ctx* c, int k);
-bool bx_fits(const amg_ctx* c, int k);
 bool bx_tuple_fits(const amg_ctx* c, int k);
+int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, PassCaller who, RankFlagsZeroed* zeroed);
+int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone, PassCaller who, RankFlagsZeroed* zeroed);
+// per claim: coverage, the fused filter, ranking (amg_build_x_claims.hip)
 int bx_nodes(amg_ctx* c, int k, Overflow* which);
-int bx_nodes_upsert(amg_ctx* c, int k, Overflow* which, bool sharded = false, bool rank_follows = true);
-int bx_nodes_rank(amg_ctx* c);
-int bx_edges(amg_ctx* c, Overflow* which, unsigned int min_edge_cov = 0);
 int bx_nodes_filtered(amg_ctx* c, int k, unsigned int min_cov, Overflow* which);
-int bx_flag_dead_reads(amg_ctx* c);
-int bx_edges_upsert(amg_ctx* c, Overflow* which, bool lone = false, bool sharded = false, bool rank_follows = true);
-int bx_edges_rank(amg_ctx* c, unsigned int min_edge_cov = 0, bool nodes_counted = false);
-int bx_node_count(amg_ctx* c, bool tag);
-int bx_bits(const amg_ctx* c, int k);
-int bx_pairs_rank(amg_ctx* c, const int* final_of_claim, int* efinal);
+int bx_edges(amg_ctx* c, Overflow* which, PassCaller who, unsigned int min_edge_cov);
+// ranking by first-seen without a sort: a bitmap over the tokens (x_rank_of, amg_slot16.h).  begin hands out the zeroed
+// flag bytes, one per token; the caller's kernel sets the byte at the first-seen position of what it ranks; finish folds
+// the bytes into bitmap words and prefix-counts them.
+struct RankBitmap {
+  const unsigned int* bits;
+  const long long* prefix;
+  const long long* total;  // device address of the number of flags set
+};
+int rank_flags_zero_behind(amg_ctx* c, ClearList* filler, RankFlagsZeroed* zeroed);  // the flag bytes join a read-back's filler
+int rank_bitmap_begin(amg_ctx* c, const RankFlagsZeroed& zeroed, unsigned char** flags);
+int rank_bitmap_finish(amg_ctx* c, RankBitmap* r);
+int rank_first_seen(amg_ctx* c, const unsigned int* first2, long long n, int shift, const RankFlagsZeroed& zeroed, RankBitmap* r);
+// a filtered build's component ids and touched reads (amg_build_x_comp.hip)
 int bx_components_from_claims(amg_ctx* c);
+int bx_flag_dead_reads(amg_ctx* c);
 int bs_count_by_slot(amg_ctx* c, CountKind what, const int* slots, int* ids_scratch, long long n, Slot* tab,
                      const unsigned int* slot_sorted, long long n_ids, unsigned int* out);  // amg_build_fp.hip
 

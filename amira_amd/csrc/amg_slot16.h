@@ -1,5 +1,6 @@
-// amg_slot16.h — the 16-byte slot of the exact-key tables and how a local key is read back out of it: what the
-// table passes (amg_x.h, amg_build_x.hip) share with the multi-GPU merge (amg_dist_local.hip, amg_dist_merge.hip).
+// amg_slot16.h — the 16-byte slot of the exact-key tables, how a local key is read back out of it, a claim's first-seen
+// and its rank: what the table passes (amg_x.h, amg_build_x.hip) share with the per-claim stage (amg_build_x_claims.hip,
+// amg_build_x_comp.hip) and the multi-GPU merge (amg_dist_local.hip, amg_dist_merge.hip).
 #pragma once
 #include "amg_device.h"
 
@@ -25,4 +26,13 @@ __device__ __forceinline__ int x_unpack(unsigned long long w1, unsigned int tag,
 __device__ __forceinline__ unsigned int x_first_inv(const unsigned int* first2, long long c) {
   const uint2 f = reinterpret_cast<const uint2*>(first2)[c];
   return f.x > f.y ? f.x : f.y;
+}
+
+// Rank of token position t among the positions flagged for a bitmap ranking (RankBitmap, amg_internal.h): the bits set
+// before t's own.  A token position opens at most one window / adjacency, so the first-seen positions of the claims are
+// distinct and the rank of a claim's first-seen position is the claim's place in first-seen order.
+__device__ __forceinline__ long long x_rank_of(unsigned int t, const unsigned int* __restrict__ bits,
+                                               const long long* __restrict__ prefix) {
+  const unsigned int w = bits[t >> 5];
+  return prefix[t >> 5] + (long long)__popc(w & ((1u << (t & 31)) - 1u));
 }

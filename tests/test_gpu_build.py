@@ -51,6 +51,12 @@ def test_tiny_known_answers(eng):
     _run(eng, {"r": ["+a", "+b", "-b", "-a"], "s": ["+a", "+b", "-b", "-a", "+c"]}, 3)
     # k = 1: every gene is a node, canonical strand is '-'
     _run(eng, {"r1": ["+a", "-b", "+c", "+a"], "r2": ["-c", "+b"], "r3": ["+d"]}, 1)
+    # four reads of exactly k genes: one window each and no adjacency, so the edge pass is followed by no ranking of
+    # edge classes; then an ordinary build on the same engine
+    c = _run(eng, {f"r{i}": [f"+g{3 * i}", f"-g{3 * i + 1}", f"+g{3 * i + 2}"] for i in range(4)}, 3)
+    assert (c["n_nodes"], c["n_pairs"], c["n_edges"]) == (4, 0, 0)
+    c = _run(eng, {"read1": ["+gene1", "-gene2", "+gene3", "-gene4"], "read2": ["+gene1", "-gene2", "+gene3"]}, 3)
+    assert (c["n_nodes"], c["n_edges"]) == (2, 2)
 
 
 def test_ragged_and_empty_reads(eng):

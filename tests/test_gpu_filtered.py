@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import procedures as P
-from helpers import live_arrays
+from helpers import live_arrays, oracle_arrays
 from test_gpu_sweep import flat_positions
 
 pytestmark = pytest.mark.gpu
@@ -128,6 +128,26 @@ def test_extreme_thresholds_and_empty_input(thr):
         a.set_reads(np.zeros(0, np.int32), np.zeros(1, np.int64), 2)
         a.build_filtered(3, 3, 1)
         assert a.counts()["n_nodes"] == 0
+        # four reads of exactly k genes at min_node_cov = 2: every node is dropped, so the node pass is followed by no
+        # ranking; then an ordinary filtered build on the same engine, its component ids against the oracle's
+        from amira_oracle import GeneMerGraph
+        lone = {f"r{i}": [f"+g{3 * i}", f"-g{3 * i + 1}", f"+g{3 * i + 2}"] for i in range(4)}
+        vocab, toks, offs, _ = tokenize(lone)
+        a.set_reads(toks, offs, vocab.two_v)
+        a.build_filtered(3, 2, 1)
+        assert a.counts()["n_windows"] == 4 and a.counts()["n_nodes"] == 0
+        reads, _, _ = P.synth_inputs(5, 60, 12, 30, 0.05)   # two genomes that share no gene: two components
+        reads.update({"x" + r: [x[0] + "x" + x[1:] for x in genes]
+                      for r, genes in P.synth_inputs(6, 40, 12, 30, 0.05)[0].items()})
+        vocab, toks, offs, ids = tokenize(reads)
+        a.set_reads(toks, offs, vocab.two_v)
+        a.build_filtered(3, 2, 1)
+        g = GeneMerGraph(reads, 3)
+        g.filter_graph(2, 1)
+        want = oracle_arrays(g, vocab, ids, offs, 3)
+        got = a.nodes()
+        assert len(want["component"]) == a.counts()["n_nodes"] and set(want["component"].tolist()) == {1, 2}
+        assert np.array_equal(got["component"], want["component"]) and np.array_equal(got["coverage"], want["coverage"])
     finally:
         a.close()
         b.close()

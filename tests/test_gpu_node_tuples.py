@@ -1,6 +1,6 @@
-"""GPU: a node's canonical tuple, first-seen position and direction (k_x_assign_nodes_ranked / k_x_assign_nodes,
-amg_build_x.hip: the tuple is the window at the first-seen position of the node, read from the reads) against the
-sequential C oracle, for every key scheme and ranking route of the exact-key build, and through build_filtered.
+"""GPU: a node's canonical tuple, first-seen position and direction (k_x_assign_nodes_ranked,
+amg_build_x_claims.hip: the tuple is the window at the first-seen position of the node, read from the reads) against the
+sequential C oracle, for every key scheme of the exact-key build, and through build_filtered.
 
 The read sets are substrings of a random genome with a few substitutions, either strand, 3 ... 70 genes long, a few
 thousand of them so that the token array spans many 1 024-token tiles, plus an empty read, reads of one and two genes
@@ -117,11 +117,11 @@ def test_fingerprint_keys_control():
     run(600, 7, 9, 2)
 
 
-@pytest.mark.parametrize("env", [{"AMG_X_TIGHT_BITS": "1"}, {"AMG_NODE_BUCKETS": "0"}, {"AMG_X_RANK_SORT": "1"},
+@pytest.mark.parametrize("env", [{"AMG_X_TIGHT_BITS": "1"}, {"AMG_NODE_BUCKETS": "0"},
                                  {"AMG_CLAIM_SHARDS": "1", "AMG_X_HEAD_TILES": "2"}],
                          ids=lambda e: "+".join(e))
 def test_switches(env, monkeypatch):
-    """tight bits, hashed slots only, the sort-path twin kernel, claim ids with holes behind a head launch"""
+    """tight bits, hashed slots only, claim ids with holes behind a head launch"""
     for key, val in env.items():
         monkeypatch.setenv(key, val)
     run(300, 7, 5, 1)
