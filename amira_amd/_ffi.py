@@ -86,6 +86,9 @@ def _load():
         "amg_remove_short_linear_paths": (C.c_int, [P, I32, P, C.POINTER(I64), P]),
         "amg_remove_low_coverage_components": (C.c_int, [P, U32]),
         "amg_get_reads_to_correct": (C.c_int, [P, P]),
+        "amg_depth_by_length": (C.c_int, [P, P, I32, P, C.POINTER(I64)]),
+        "amg_remove_non_amr_nodes": (C.c_int, [P, P, C.POINTER(I64)]),
+        "amg_component_amr_reads": (C.c_int, [P, P, I32, I64, P, P, C.POINTER(I64)]),
         "amg_correct_reads": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64)]),
         "amg_get_corrected": (C.c_int, [P, P, P, P, P, P, P]),
         "amg_get_corrected32": (C.c_int, [P, P, P, P, P, P, P, P, C.POINTER(I64)]),

@@ -601,6 +601,8 @@ class GeneMerGraph(BubblePopping):
                 eng.remove_low_coverage_components(arg)
             elif what == "remove_short_linear_paths":
                 eng.remove_short_linear_paths(*arg)
+            elif what == "remove_non_amr_nodes":
+                eng.remove_non_amr_nodes(arg)
         self._pass_log = list(state["passes"])
         self._minNodeCoverage, self._minEdgeCoverage = state["min_cov"]
         self._extra_to_correct = set(state["extra_to_correct"])
@@ -1158,8 +1160,26 @@ class GeneMerGraph(BubblePopping):
             self._invalidate()
         return hashes
 
+    def _gene_flags(self, genes):
+        """a byte per gene rank, 1 for the genes named (what the engine's read walks take); unknown names flag nothing"""
+        flags = np.zeros(self._vocab.two_v // 2, np.uint8)
+        for g in genes:
+            r = self._vocab.rank.get(g)
+            if r is not None:
+                flags[r] = 1
+        return flags
+
     def remove_non_AMR_associated_nodes(self, genesOfInterest):
         """drop every node none of whose reads touches a node holding a gene of interest (:2941-2959)."""
+        if not self._host_edits:
+            # one walk over the reads on the device (amg_remove_non_amr_nodes): no view, no id list
+            self._settle_leases()
+            flags = self._gene_flags(list(genesOfInterest))
+            removed = self._engine.remove_non_amr_nodes(flags)
+            self._pass_log.append(("remove_non_amr_nodes", flags))
+            if removed:
+                self._invalidate()
+            return
         v = self._v()
         amr_ids = self._node_ids_containing(list(genesOfInterest))
         tok_node = v.arrays["tok_node"]

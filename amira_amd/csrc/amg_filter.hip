@@ -331,7 +331,7 @@ __global__ void k_scatter_ids(const unsigned char* __restrict__ killed, const lo
 }
 
 // kill[] (s0) -> node_alive, removal side effects, ascending list of removed ids
-static int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids) {
+int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids) {
   hipStream_t st = c->stream;
   const long long D = c->n_nodes;
   AMGCHK(c->s2.ensure((size_t)(D + 2) * sizeof(long long)));

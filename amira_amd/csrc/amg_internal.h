@@ -427,6 +427,9 @@ GView make_view(amg_ctx* c);
 void live_lists_after_node_deaths(amg_ctx* c);  // nodes died, and every edge that died has a dead end
 void live_lists_after_edge_deaths(amg_ctx* c);  // an edge died with both its ends alive
 void live_lists_after_build(amg_ctx* c);        // a new graph
+// amg_filter.hip: the nodes marked in s0 (a byte each, D + 8 bytes zeroed before the marking) die, with everything a
+// removal brings: edges, masked windows, read_fix, live lists.  Uses s2 (and s3 for the ids); waits for the count.
+int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids);
 void bubbles_release(amg_ctx* c);  // amg_bubbles.hip
 void sketch_release(amg_ctx* c);   // amg_sketch.hip
 void pop_release(amg_ctx* c);  // amg_pop.hip

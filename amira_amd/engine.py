@@ -19,6 +19,7 @@ class Engine:
         # there are any, the engine stays out of the pool
         self._leases = weakref.WeakSet()
         self._pool_when_free = False
+        self._two_v = None   # of the current read set, where it came through set_reads* (checks the gene flags' length)
         # of pop_rewrite, over the engine's life; declined: correct_bubble_paths calls that went to the host loop
         # because their input is beyond the call's limits
         self.pop_rewrite_stats = {"calls": 0, "reads": 0, "rewritten": 0, "declined": 0}
@@ -40,12 +41,14 @@ class Engine:
         read_offsets = np.ascontiguousarray(read_offsets, dtype=np.int64)
         check(_ffi.lib.amg_set_reads(self._h, ptr(tokens), ptr(read_offsets),
                                      len(read_offsets) - 1, int(two_v), 0))
+        self._two_v = int(two_v)
 
     def set_reads_device(self, tokens_ptr, read_offsets_ptr, n_reads, two_v, borrow=False):
         """device pointers; borrow=True: no copy, the caller keeps the arrays alive and unchanged
         until the next set_reads* / adopt_corrected"""
         check(_ffi.lib.amg_set_reads(self._h, C.c_void_p(tokens_ptr), C.c_void_p(read_offsets_ptr),
                                      int(n_reads), int(two_v), 2 if borrow else 1))
+        self._two_v = int(two_v)
 
     def set_positions(self, gene_start, gene_end, read_len=None):
         """int32 arrays travel as they are (amg_set_positions32: half the bytes over PCIe), anything else as int64"""
@@ -88,6 +91,8 @@ class Engine:
         handles = (C.c_void_p * n)(*[e._h for e in engines])
         arr = (C.c_int32 * n)(*[int(k) for k in ks])
         check(_ffi.lib.amg_build_multi(handles, arr, n))
+        for e in engines[1:]:
+            e._two_v = engines[0]._two_v
 
     def finalize(self):
         """component ids + per-node edge lists of the built graph now (they are otherwise made on first use)"""
@@ -237,6 +242,39 @@ class Engine:
     def remove_low_coverage_components(self, min_cov):
         check(_ffi.lib.amg_remove_low_coverage_components(self._h, int(min_cov)))
 
+    # ---- read walks (include/amg.h: amg_depth_by_length, amg_remove_non_amr_nodes, amg_component_amr_reads)
+    def depth_by_length(self, min_genes):
+        """(pairs, n_alive): pairs[j] = distinct (read, node) pairs with a live window of the read on the node over the
+        reads of at least min_genes[j] genes (at most 16 lengths a call), n_alive = alive nodes"""
+        mg = np.ascontiguousarray(min_genes, dtype=np.int32)
+        pairs, n_alive = np.zeros(max(len(mg), 1), np.int64), C.c_int64(0)
+        check(_ffi.lib.amg_depth_by_length(self._h, ptr(mg), len(mg), ptr(pairs), C.byref(n_alive)))
+        return pairs[:len(mg)], n_alive.value
+
+    def _gene_flags(self, flags):
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        # (the library reads two_v / 2 bytes; two_v is known here for reads that came through set_reads*)
+        assert self._two_v is None or len(flags) == self._two_v // 2, "one flag per gene rank (two_v / 2 of them)"
+        return flags
+
+    def remove_non_amr_nodes(self, flags):
+        """every alive node that no read with a live window on a gene of interest reaches dies (flags: a byte per gene
+        rank, non-zero = gene of interest); returns how many"""
+        flags = self._gene_flags(flags)
+        n = C.c_int64(0)
+        check(_ffi.lib.amg_remove_non_amr_nodes(self._h, ptr(flags), C.byref(n)))
+        return n.value
+
+    def component_amr_reads(self, flags, min_genes):
+        """(n_reads, n_long), entry c for the component with id c + 1: the reads with a live window on a gene of
+        interest in the component, and those of them with at least min_genes genes"""
+        flags = self._gene_flags(flags)
+        cap = max(self.graph_sizes()[0], 1)   # (no more components than nodes: one call, pages beyond the answer untouched)
+        n_reads, n_long, nc = np.empty(cap, np.int64), np.empty(cap, np.int64), C.c_int64(0)
+        check(_ffi.lib.amg_component_amr_reads(self._h, ptr(flags), int(min_genes), cap, ptr(n_reads), ptr(n_long),
+                                               C.byref(nc)))
+        return n_reads[:nc.value].copy(), n_long[:nc.value].copy()
+
     def correct_reads(self):
         nr, nt = C.c_int64(0), C.c_int64(0)
         check(_ffi.lib.amg_correct_reads(self._h, C.byref(nr), C.byref(nt)))
@@ -332,6 +370,7 @@ class Engine:
         """this engine's read set := the corrected set of engine `src` (genes, offsets, positions, read lengths),
         device to device"""
         check(_ffi.lib.amg_set_reads_from_corrected(self._h, src._h))
+        self._two_v = src._two_v
 
     # ---- K6: batched exact sub-list search
     def match_patterns(self, which, patterns):

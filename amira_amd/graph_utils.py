@@ -11,6 +11,7 @@ on the device and `cores` is accepted for signature compatibility only.
 """
 import statistics
 import os
+from fractions import Fraction
 import sys
 
 import numpy as np
@@ -199,18 +200,12 @@ def choose_kmer_size(overall_mean_node_coverage, new_annotatedReads, cores, new_
         # amg_build_multi) instead of making two each
         reads_t, pos_t = _tokenized(new_annotatedReads, new_gene_position_dict)
         graphs = GeneMerGraph.build_many(reads_t, list(range(3, 16, 2)), pos_t)
+        flags = graphs[0]._gene_flags(sample_genesOfInterest)   # (one vocabulary for the seven graphs)
         for k, graph in zip(range(3, 16, 2), graphs):
-            amr = {n.__hash__() for g in sample_genesOfInterest for n in graph.get_nodes_containing(g)}
-
-            def is_component_valid(component):
-                members = [n.__hash__() for n in graph.get_nodes_in_component(component)]
-                reads = graph.collect_reads_in_path([h for h in members if h in amr])
-                lengths = [len(graph.get_reads()[r]) for r in reads]
-                if len(lengths) == 0:
-                    return True
-                return len([x for x in lengths if x >= (2 * k - 1)]) / len(lengths) >= 0.8
-
-            if all(is_component_valid(c) for c in graph.components()):
+            # per component, the reads through its AMR nodes and those of them with 2k - 1 genes: one walk over the
+            # reads on the device (amg_component_amr_reads) — no Node object, hash or view is made
+            n_reads, n_long = graph._engine.component_amr_reads(flags, 2 * k - 1)
+            if all(n == 0 or m / n >= 0.8 for n, m in zip(n_reads.tolist(), n_long.tolist())):
                 geneMer_size = k
             else:
                 break
@@ -221,7 +216,17 @@ def choose_kmer_size(overall_mean_node_coverage, new_annotatedReads, cores, new_
 
 def get_overall_mean_node_coverages(graph):
     """mean over nodes of the number of the node's reads with >= k genes, k = 3,5,..,15
-    (graph_utils.py:299-313) — from the device's node->reads CSR."""
+    (graph_utils.py:299-313) — one walk over the reads on the device (amg_depth_by_length): the sum over nodes is the
+    number of distinct (read, node) pairs among the reads of that length.  A graph edited by hand is answered from the
+    device's node->reads CSR as before."""
+    if not graph._host_edits:
+        ks = list(range(3, 16, 2))
+        pairs, n_alive = graph._engine.depth_by_length(ks)
+        out = {}
+        for k, p in zip(ks, pairs.tolist()):
+            # statistics.mean of a list of ints: the int when the division is exact, else the correctly rounded float
+            out[k] = 0 if n_alive == 0 else (p // n_alive if p % n_alive == 0 else float(Fraction(p, n_alive)))
+        return out
     off, idx = graph._engine.node_reads()
     alive = graph._engine.nodes()["alive"] != 0
     read_len = np.diff(graph._read_off)

@@ -206,6 +206,26 @@ int amg_remove_low_coverage_components(amg_ctx* ctx, uint32_t min_component_cove
 /* get_reads_to_correct() as a 0/1 flag per read (construct_graph.py:148-150) */
 int amg_get_reads_to_correct(amg_ctx* ctx, uint8_t* flags);
 
+/* ---- read walks: what the drivers ask of every read before the first cleaning sweep, from the token stream and the
+ *      per-window node ids on the device (amira_amd/csrc/amg_read_walk.hip).  A window is LIVE when its node id is >= 0
+ *      and the node alive.  gene_flags: two_v / 2 HOST bytes indexed by gene rank, non-zero = gene of interest; a
+ *      window is an AMR window when one of its k genes is flagged (== its node's canonical gene-mer holds the gene).
+ *      AMG_E_STATE on a graph made by amg_dist_merge* (the ctx holds only its shard of the reads). -------------- */
+/* get_overall_mean_node_coverages (graph_utils.py:299-313): pairs[j] = distinct (read, node) pairs with a live window
+ * of the read on the node, over the reads of at least min_genes[j] genes (a node a read visits twice counts once,
+ * construct_node.py:64-67); *n_alive = alive nodes; the mean over nodes is pairs[j] / n_alive.  n in [1, 16]. */
+int amg_depth_by_length(amg_ctx* ctx, const int32_t* min_genes, int32_t n, int64_t* pairs, int64_t* n_alive);
+/* remove_non_AMR_associated_nodes (construct_graph.py:2941-2959): every alive node on which no read with a live AMR
+ * window has a live window is removed, as by amg_remove_nodes; *n_removed = their number.  No id list leaves or
+ * enters the device. */
+int amg_remove_non_amr_nodes(amg_ctx* ctx, const uint8_t* gene_flags, int64_t* n_removed);
+/* per component, the reads choose_kmer_size looks at (graph_utils.py:258-296): entry c describes the component whose
+ * id (amg_get_nodes, `component`: ids start at 1) is c + 1; n_reads[c] = reads with a live AMR window on a node of the
+ * component — a read counts once per component —, n_long[c] = those of them with at least min_genes genes.
+ * *n_components is always written; cap < *n_components is AMG_E_ARG (size the arrays and call again). */
+int amg_component_amr_reads(amg_ctx* ctx, const uint8_t* gene_flags, int32_t min_genes, int64_t cap, int64_t* n_reads,
+                            int64_t* n_long, int64_t* n_components);
+
 /* ---- per-read correction: correct_reads (construct_graph.py:1123-1396,1433-1480) --- */
 /* Re-threads every marked read through the filtered graph on the device and leaves
  * the corrected read set in ctx.  Outputs: reads kept (marked reads whose nodes were
