@@ -71,7 +71,7 @@ __device__ __forceinline__ int bj_edges_between(const GView& g, int a, int b) {
 
 #define BJ_MULTI 1ull    // a path ends at a junction over a pair of nodes with more than one edge between them
 #define BJ_BUDGET 2ull   // a search was abandoned
-#define BJ_STEPS (1ull << 24)
+#define BJ_STEPS (1ull << 24)   // nodes a search may enter; AMG_TEST_BJ_STEPS=n (test hook, 1 <= n <= 2^24) asks for fewer
 
 // One WAVE per start junction, the search run cooperatively (wave_dfs, amg_wave_dfs.h: stack level d lives in lane d).
 // A node entered at depth d >= 1 with L = d + 1 <= distance nodes on the path that is a junction on the side the
@@ -90,9 +90,9 @@ struct BjVisit {
   long long j;
   int distance, lane;
   long long n_rec, n_int;
-  unsigned long long steps, bad;
+  unsigned long long budget, steps, bad;
   __device__ __forceinline__ int enter(int d, int L, int cur_node, int cur_dir, int my_node, int my_dir) {
-    if (++steps > BJ_STEPS) {
+    if (++steps > budget) {
       bad |= BJ_BUDGET;
       return WD_ABORT;
     }
@@ -126,7 +126,8 @@ struct BjVisit {
 template <bool EMIT>
 __global__ __launch_bounds__(64) void k_bj_dfs(GView g, const int* __restrict__ jrows, long long J,
                                                const unsigned char* __restrict__ jflag, const long long* __restrict__ jpos,
-                                               int distance, long long* __restrict__ cnt_rec, long long* __restrict__ cnt_int,
+                                               int distance, unsigned long long budget, long long* __restrict__ cnt_rec,
+                                               long long* __restrict__ cnt_int,
                                                const long long* __restrict__ rec_base, const long long* __restrict__ int_base,
                                                int* __restrict__ rec_stop, long long* __restrict__ rec_off,
                                                int* __restrict__ pool_node, signed char* __restrict__ pool_dir,
@@ -135,7 +136,8 @@ __global__ __launch_bounds__(64) void k_bj_dfs(GView g, const int* __restrict__ 
   if (j >= J) return;
   const int lane = threadIdx.x;
   const int row0 = jrows[j];
-  BjVisit<EMIT> v{g, jflag, jpos, rec_base, int_base, rec_stop, rec_off, pool_node, pool_dir, j, distance, lane, 0, 0, 0, 0};
+  BjVisit<EMIT> v{g, jflag, jpos, rec_base, int_base, rec_stop, rec_off, pool_node, pool_dir, j, distance, lane, 0, 0,
+                  budget, 0, 0};
   wave_dfs(g, row0 >> 1, (row0 & 1) ? -1 : 1, lane, v);
   if (lane == 0) {
     if (!EMIT) {
@@ -150,6 +152,11 @@ extern "C" int amg_junction_paths(amg_ctx* c, int32_t max_distance, int64_t* siz
   NEED_BUILT(c);
   if (!sizes) return amg_fail(AMG_E_ARG, "null argument");
   if (max_distance < 2 || max_distance > 64) return amg_fail(AMG_E_ARG, "max_distance must be in [2, 64]");
+  unsigned long long budget = BJ_STEPS;
+  if (const char* e = getenv("AMG_TEST_BJ_STEPS")) {  // test hook: read on every call, never more than the default
+    const long long n = atoll(e);
+    budget = n < 1 ? 1ull : ((unsigned long long)n < BJ_STEPS ? (unsigned long long)n : BJ_STEPS);
+  }
   BubbleState* b = bub_of(c);
   b->j_node.clear(); b->j_dir.clear(); b->p_start.clear(); b->p_off.assign(1, 0); b->p_node.clear(); b->p_dir.clear();
   sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0;
@@ -188,8 +195,8 @@ extern "C" int amg_junction_paths(amg_ctx* c, int32_t max_distance, int64_t* siz
   hipLaunchKernelGGL(k_bj_rows, dim3(nblk(rows, 256)), dim3(256), 0, st, b->jflag.as<unsigned char>(), b->jpos.as<long long>(),
                      rows, b->jrows.as<int>());
   hipLaunchKernelGGL(k_bj_dfs<false>, dim3((unsigned int)J), dim3(64), 0, st, g, b->jrows.as<int>(), J,
-                     b->jflag.as<unsigned char>(), b->jpos.as<long long>(), (int)max_distance, b->cnt_rec.as<long long>(),
-                     b->cnt_int.as<long long>(), (const long long*)nullptr, (const long long*)nullptr, (int*)nullptr,
+                     b->jflag.as<unsigned char>(), b->jpos.as<long long>(), (int)max_distance, budget,
+                     b->cnt_rec.as<long long>(), b->cnt_int.as<long long>(), (const long long*)nullptr, (const long long*)nullptr, (int*)nullptr,
                      (long long*)nullptr, (int*)nullptr, (signed char*)nullptr, flags);
   AMGCHK(prim_exscan_i64_pair(c, b->cnt_rec.as<long long>(), b->rec_base.as<long long>(), b->cnt_int.as<long long>(),
                               b->int_base.as<long long>(), (size_t)J));
@@ -214,8 +221,8 @@ extern "C" int amg_junction_paths(amg_ctx* c, int32_t max_distance, int64_t* siz
     AMGCHK(b->pool_node.ensure((size_t)(N + 1) * sizeof(int)));
     AMGCHK(b->pool_dir.ensure((size_t)N + 64));
     hipLaunchKernelGGL(k_bj_dfs<true>, dim3((unsigned int)J), dim3(64), 0, st, g, b->jrows.as<int>(), J,
-                       b->jflag.as<unsigned char>(), b->jpos.as<long long>(), (int)max_distance, (long long*)nullptr,
-                       (long long*)nullptr, b->rec_base.as<long long>(), b->int_base.as<long long>(), b->rec_stop.as<int>(),
+                       b->jflag.as<unsigned char>(), b->jpos.as<long long>(), (int)max_distance, budget,
+                       (long long*)nullptr, (long long*)nullptr, b->rec_base.as<long long>(), b->int_base.as<long long>(), b->rec_stop.as<int>(),
                        b->rec_off.as<long long>(), b->pool_node.as<int>(), b->pool_dir.as<signed char>(), flags);
     HIPCHK(hipMemcpyAsync(rec_base.data(), b->rec_base.p, (size_t)(J + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(rec_off.data(), b->rec_off.p, (size_t)R * sizeof(long long), hipMemcpyDeviceToHost, st));

@@ -297,7 +297,8 @@ int amg_minhash(amg_ctx* ctx, const uint8_t* bases, const int64_t* seg_off, cons
  *      leave a component, so the caller splits the list by the component of the start.
  *      sizes[0] = junctions, [1] = paths, [2] = nodes over all paths, [3] = flags: bit 0 — a path ends at a junction
  *      over two nodes with more than one edge between them, where the reference fails (:1515-1523 on a list); bit 1 —
- *      a search was abandoned after 2^24 steps.  With a flag set the paths are not to be used.
+ *      a search was abandoned after 2^24 steps (test hook AMG_TEST_BJ_STEPS=n: after n).  With a flag set the paths
+ *      are not to be used.
  *      amg_get_junction_paths copies out: junction_node / junction_dir [junctions], path_start [paths] (index of the
  *      start junction), path_off [paths + 1], path_node / path_dir [sizes[2]]; any pointer may be NULL. ---------- */
 int amg_junction_paths(amg_ctx* ctx, int32_t max_distance, int64_t* sizes /*[4]*/);
