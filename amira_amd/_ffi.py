@@ -39,6 +39,7 @@ class Xfer(C.Structure):
 
 
 XFER_ALL_TO_ALL, XFER_ALL_GATHER = 1, 2
+WALK_DEPTH, WALK_AMR_TRIM, WALK_COMPONENT_READS = 1, 2, 3   # include/amg.h AMG_WALK_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -119,6 +120,11 @@ def _load():
         "amg_dist_merge_begin": (C.c_int, [P, I32, U32, U32]),
         "amg_dist_merge_next": (C.c_int, [P, C.POINTER(Xfer)]),
         "amg_dist_merge_local": (C.c_int, [C.POINTER(P), I32, I32, U32, U32]),
+        "amg_dist_walk": (C.c_int, [P, I32, P, P, I32, P, I64, C.POINTER(I64)]),
+        "amg_dist_walk_local": (C.c_int, [C.POINTER(P), I32, I32, P, P, I32, P, I64, C.POINTER(I64)]),
+        "amg_dist_walk_begin": (C.c_int, [P, I32, P, P, I32]),
+        "amg_dist_walk_next": (C.c_int, [P, C.POINTER(Xfer)]),
+        "amg_dist_walk_result": (C.c_int, [P, P, I64, C.POINTER(I64)]),
         "amg_copy_d2h": (C.c_int, [P, P, P, I64]),
         "amg_copy_h2d": (C.c_int, [P, P, P, I64]),
         "amg_dist_stats": (C.c_int, [P, C.POINTER(I64), I32]),

@@ -3,6 +3,7 @@
 //   amg_dist.hip        RCCL, the driver (one function per state), the derived rebuild, the transports, statistics
 //   amg_dist_local.hip  phase local: the shard's tables -> records by destination, the count message
 //   amg_dist_merge.hip  phases reduce, hold and global
+//   amg_dist_walk.hip   the read walks across ranks: a second, small state machine over the same rank, world and transports
 #pragma once
 #include <chrono>
 #include <string>
@@ -56,6 +57,24 @@ enum DistStat {
   DS_N
 };
 
+// ---- a read walk across ranks (amg_dist_walk.hip): local phase -> header exchange -> verdict -> data exchange -> fold
+enum { W_IDLE = 0, W_LOCAL, W_JUDGE, W_FOLD };
+struct WalkState {
+  int state = W_IDLE, which = 0;
+  int32_t n = 0;
+  std::vector<int32_t> min_genes;
+  std::vector<uint8_t> gene_flags;
+  std::vector<unsigned int> flag_words;  // the flag bitmap while the stream takes it
+  int64_t hdr[8] = {0};                  // this rank's header (amg_dist_walk_hdr.h)
+  int fail_ret = 0;                      // a failure of the local phase, told in the header
+  std::string fail_msg;
+  int64_t data_words = 0;                // 64-bit words a rank contributes to the data exchange
+  DevBuf msg, msg_all;                   // this rank's header (+ the depth sums), the headers of all ranks: made at begin
+  DevBuf send, recv;                     // the data exchange: this rank's part / the folded answer, the parts of all ranks
+  bool have_result = false;
+  std::vector<int64_t> result;           // amg_dist_walk_result
+};
+
 struct DistState {
   int rank = 0, world = 1;
   ncclComm_t comm = nullptr;
@@ -94,12 +113,28 @@ struct DistState {
   bool time_phases = false;
   int phase_now = -1;
   std::chrono::steady_clock::time_point phase_t0;
+  WalkState walk;
 };
 
 // order in which the local records leave (nullptr: local order); the bucketing ran over d->nspace ids
 static inline const unsigned int* send_order(const DistState* d) {
   return d->sorted ? d->loc_bucket.as<unsigned int>() + 3 * (d->nspace + 1) : nullptr;
 }
+
+// ------------------------------------------------------------------ what the merge and the walks share (amg_dist.hip)
+// entry points that need no graph yet start with this
+#define NEED_CTX(c)                                              \
+  do {                                                           \
+    if (!(c)) return amg_fail(AMG_E_ARG, "null ctx");            \
+    HIPCHK(hipSetDevice((c)->device));                           \
+  } while (0)
+DistState* dist_state(amg_ctx* c);                 // the ctx's state, made on first use
+bool dist_on_wire(const DistState* d);             // more than one rank, or the test hook: exchanges are performed
+// *x = an all-gather of `count` elements per rank; booked in the statistics (stat: its bytes as well)
+void dist_xfer_ag(DistState* d, amg_xfer* x, const void* send, void* recv, int elem_bytes, int64_t count, bool stat);
+int dist_rccl_perform(amg_ctx* c, DistState* d, const amg_xfer& x);  // one exchange over RCCL, on the ctx's stream
+// emulated ranks: xs[r] is what rank r = ctxs[r] asked for; performed as device copies, waited for
+int dist_local_exchange(amg_ctx* const* ctxs, int world, const amg_xfer* xs);
 
 // ------------------------------------------------------------------ the device phases (all on the ctx's stream)
 // amg_dist_local.hip

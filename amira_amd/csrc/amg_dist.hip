@@ -27,22 +27,17 @@
 // RCCL (ncclSend / ncclRecv groups and ncclAllGather on the ctx's stream; librccl is opened at amg_dist_init, not
 // linked), amg_dist_merge_local with device copies between the ctxs of one process (emulated ranks: tests, the scaling
 // model), and amg_dist_merge_begin / _next hand them to the caller (tests between processes over gloo).
+// The read walks of a merged graph (amg_dist_walk.hip) travel over the same three transports.
 #include <dlfcn.h>
 
 #include "amg_dist.h"
-
-#define NEED_CTX(c)                                              \
-  do {                                                           \
-    if (!(c)) return amg_fail(AMG_E_ARG, "null ctx");            \
-    HIPCHK(hipSetDevice((c)->device));                           \
-  } while (0)
 
 static const char* const kPhaseNames[2 * S_N] = {  // [kind * S_N + state]
     "", "nodes_local", "nodes_counts_pack", "nodes_reduce", "nodes_hold", "nodes_hcounts", "nodes_global",
     "derive_local", "derive_ask", "derive_fill",
     "", "edges_local", "edges_counts_pack", "edges_reduce", "edges_hold", "edges_hcounts", "edges_global", "", "", ""};
 
-static DistState* dm(amg_ctx* c) {
+DistState* dist_state(amg_ctx* c) {
   if (!c->dist) c->dist = new DistState();
   return c->dist;
 }
@@ -93,7 +88,8 @@ void dist_release(amg_ctx* c) {
   if (d->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d->comm);
   DevBuf* all[] = {&d->cnt_send, &d->cnt_recv, &d->hc_send,    &d->hc_recv,      &d->offs,      &d->send,
                    &d->recv,     &d->rep_out,  &d->rep_in,     &d->held,         &d->held_pad,  &d->gathered,
-                   &d->own_tab,  &d->loc_cnt,  &d->loc_bucket, &d->loc_dest_cnt, &d->loc_first, &d->loc_slot};
+                   &d->own_tab,  &d->loc_cnt,  &d->loc_bucket, &d->loc_dest_cnt, &d->loc_first, &d->loc_slot,
+                   &d->walk.msg, &d->walk.msg_all, &d->walk.send, &d->walk.recv};
   for (DevBuf* b : all) b->release();
   delete d;
   c->dist = nullptr;
@@ -101,8 +97,9 @@ void dist_release(amg_ctx* c) {
 
 static int set_world(amg_ctx* c, int rank, int world) {
   if (world < 1 || rank < 0 || rank >= world) return amg_fail(AMG_E_ARG, "bad rank %d / world %d", rank, world);
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   if (d->state != S_IDLE) return amg_fail(AMG_E_STATE, "a merged build is under way");
+  d->walk.state = W_IDLE;  // (a walk somebody abandoned ends here)
   if (d->comm) {
     (void)g_rccl.CommDestroy(d->comm);
     d->comm = nullptr;
@@ -121,7 +118,7 @@ extern "C" int amg_dist_init(amg_ctx* c, const void* unique_id, int32_t rank, in
   AMGCHK(set_world(c, rank, world));
   ncclUniqueId id;
   memcpy(&id, unique_id, sizeof(id));
-  NCCLCHK(g_rccl.CommInitRank(&dm(c)->comm, world, id, rank));
+  NCCLCHK(g_rccl.CommInitRank(&dist_state(c)->comm, world, id, rank));
   return AMG_OK;
 }
 
@@ -216,7 +213,7 @@ static void xfer_a2a(DistState* d, amg_xfer* x, const void* send, void* recv, in
   }
 }
 
-static void xfer_ag(DistState* d, amg_xfer* x, const void* send, void* recv, int elem_bytes, int64_t count, bool stat) {
+void dist_xfer_ag(DistState* d, amg_xfer* x, const void* send, void* recv, int elem_bytes, int64_t count, bool stat) {
   x->kind = AMG_XFER_ALL_GATHER;
   x->elem_bytes = elem_bytes;
   x->send = send;
@@ -283,11 +280,11 @@ typedef int Step;
 enum { STEP_DONE = 0 /* the build is complete */, STEP_XFER = 1 /* perform *x, then come back */, STEP_ON = 2 /* d->state next */ };
 
 // one rank sends nothing (what it packs is what arrives) unless the test hook asks for it
-static bool on_wire(const DistState* d) { return d->world > 1 || d->always_exchange; }
+bool dist_on_wire(const DistState* d) { return d->world > 1 || d->always_exchange; }
 
 static Step st_local(amg_ctx* c, DistState* d, amg_xfer* x) {
   const int is_edge = d->kind, W = d->world;
-  const bool wire = on_wire(d);
+  const bool wire = dist_on_wire(d);
   const int r = is_edge ? edges_local(c, d) : nodes_local(c, d);
   if (r != AMG_OK) {
     if (!wire) {
@@ -316,7 +313,7 @@ static Step st_local(amg_ctx* c, DistState* d, amg_xfer* x) {
 
 static Step st_counts(amg_ctx* c, DistState* d, amg_xfer* x) {
   const int is_edge = d->kind, W = d->world;
-  const bool wire = on_wire(d);
+  const bool wire = dist_on_wire(d);
   if (wire) {
     const int v = read_and_judge(c, d, CNT_WORDS, 2, d->cnt_recv.p, d->cnt_send.p);
     if (v != 0) return v < 0 ? v : STEP_ON;
@@ -368,7 +365,7 @@ static Step st_counts(amg_ctx* c, DistState* d, amg_xfer* x) {
 
 static Step st_reduce(amg_ctx* c, DistState* d, amg_xfer* x) {
   const int is_edge = d->kind;
-  const bool wire = on_wire(d);
+  const bool wire = dist_on_wire(d);
   // (one rank, nothing on the wire: what was packed is what arrives, and the answers are read where they are written)
   d->recv_p = wire ? d->recv.p : d->send.p;
   d->rep_out_p = wire ? d->rep_out.p : d->rep_in.p;
@@ -391,14 +388,14 @@ static Step st_hold(amg_ctx* c, DistState* d, amg_xfer* x) {
   stage_end(c);
   if (r != AMG_OK) return r;
   d->state = S_HCOUNTS;
-  if (!on_wire(d)) return STEP_ON;
-  xfer_ag(d, x, d->hc_send.p, d->hc_recv.p, HC_WORDS * (int)sizeof(long long), 1, false);
+  if (!dist_on_wire(d)) return STEP_ON;
+  dist_xfer_ag(d, x, d->hc_send.p, d->hc_recv.p, HC_WORDS * (int)sizeof(long long), 1, false);
   return STEP_XFER;
 }
 
 static Step st_hcounts(amg_ctx* c, DistState* d, amg_xfer* x) {
   const int is_edge = d->kind, W = d->world;
-  const bool wire = on_wire(d);
+  const bool wire = dist_on_wire(d);
   const void* msg = wire ? d->hc_recv.p : d->hc_send.p;
   const int v = read_and_judge(c, d, HC_WORDS, 1, msg);
   if (v != 0) return v < 0 ? v : STEP_ON;
@@ -432,7 +429,7 @@ static Step st_hcounts(amg_ctx* c, DistState* d, amg_xfer* x) {
   }
   AMGCHK(d->gathered.ensure((size_t)W * (size_t)d->m_pad * hb));
   d->gathered_p = d->gathered.p;
-  xfer_ag(d, x, src, d->gathered.p, hb, d->m_pad, true);
+  dist_xfer_ag(d, x, src, d->gathered.p, hb, d->m_pad, true);
   return STEP_XFER;
 }
 
@@ -507,7 +504,7 @@ static Step st_dv_local(amg_ctx* c, DistState* d, amg_xfer* x) {
     AMGCHK(derive_local(c, d->k, d->dv_bases[d->rank], d->tokens[d->rank], d->offs.as<long long>(), W,
                         d->dv_bounds.data(), &d->dv_D2, &d->dv_P2, &d->dv_ok));
   }
-  if (!on_wire(d)) {
+  if (!dist_on_wire(d)) {
     if (!d->dv_ok) {
       d->state = S_LOCAL;
       return STEP_ON;
@@ -521,7 +518,7 @@ static Step st_dv_local(amg_ctx* c, DistState* d, amg_xfer* x) {
   AMGCHK(d->cnt_recv.ensure((size_t)W * CNT_WORDS * sizeof(long long)));
   hipLaunchKernelGGL(k_dv_msg, dim3(1), dim3(1), 0, c->stream, d->dv_ok ? 1ll : 0ll, (long long)c->n_tokens,
                      (long long)d->attempt, d->dv_ok ? d->dv_D2 : -1ll, d->cnt_send.as<long long>());
-  xfer_ag(d, x, d->cnt_send.p, d->cnt_recv.p, CNT_WORDS * (int)sizeof(long long), 1, false);
+  dist_xfer_ag(d, x, d->cnt_send.p, d->cnt_recv.p, CNT_WORDS * (int)sizeof(long long), 1, false);
   d->state = S_DV_ASK;
   return STEP_XFER;
 }
@@ -555,7 +552,7 @@ static Step st_dv_ask(amg_ctx* c, DistState* d, amg_xfer* x) {
                      nb[d->rank + 1] - nb[d->rank], (long long)(base << 1), c->alt_pfirst.as<unsigned long long>() + pb[d->rank],
                      pb[d->rank + 1] - pb[d->rank], (unsigned long long)base << 3, d->dv_mN, d->dv_mP,
                      d->held.as<unsigned long long>());
-  xfer_ag(d, x, d->held.p, d->gathered.p, (int)sizeof(unsigned long long), m, true);
+  dist_xfer_ag(d, x, d->held.p, d->gathered.p, (int)sizeof(unsigned long long), m, true);
   return STEP_XFER;
 }
 
@@ -577,7 +574,7 @@ static constexpr decltype(&st_local) kStates[S_N] = {nullptr,    st_local,    st
 
 // runs the machine up to its next exchange.  1: *x is to be performed, then call again; 0: the build is complete
 static int advance(amg_ctx* c, amg_xfer* x) {
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   for (;;) {
     if (d->state <= S_IDLE || d->state >= S_N) return amg_fail(AMG_E_STATE, "amg_dist_merge_begin first");
     phase_tick(c, d, d->kind * S_N + d->state);
@@ -590,13 +587,14 @@ extern "C" int amg_dist_merge_begin(amg_ctx* c, int32_t k, uint32_t min_node_cov
   NEED_CTX(c);
   if (k < 1 || k > AMG_MAX_K) return amg_fail(AMG_E_ARG, "k must be in [1, %d]", AMG_MAX_K);
   if (c->two_v <= 0) return amg_fail(AMG_E_STATE, "amg_set_reads first");
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   d->k = k;
   d->mn = min_node_cov < 1 ? 1 : min_node_cov;
   d->me = min_edge_cov < 1 ? 1 : min_edge_cov;
   d->attempt = 0;
   d->kind = 0;
   d->fail_ret = 0;
+  d->walk.state = W_IDLE;  // (a walk somebody abandoned ends here: the graph it asked about is being replaced)
   // the reads are what a correction left of the reads of the merged graph still held (amg_adopt_corrected), same k, plain
   // build: the ranks first find out whether that graph's live part will do (S_DV_*; AMG_NO_DERIVE=1: A/B + test switch)
   const bool candidate = c->dist_candidate && c->dist_mode && c->world == d->world && k == c->k && d->mn == 1 && d->me == 1 &&
@@ -609,7 +607,7 @@ extern "C" int amg_dist_merge_begin(amg_ctx* c, int32_t k, uint32_t min_node_cov
 extern "C" int amg_dist_merge_next(amg_ctx* c, amg_xfer* out) {
   NEED_CTX(c);
   if (!out) return amg_fail(AMG_E_ARG, "null xfer");
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   if (d->state == S_IDLE) return amg_fail(AMG_E_STATE, "amg_dist_merge_begin first");
   const int r = advance(c, out);
   if (r <= 0) d->state = S_IDLE;  // (complete, or failed: the one place that puts the machine to rest)
@@ -618,7 +616,7 @@ extern "C" int amg_dist_merge_next(amg_ctx* c, amg_xfer* out) {
 }
 
 // ---- the exchanges over RCCL, on the ctx's stream
-static int rccl_perform(amg_ctx* c, DistState* d, const amg_xfer& x) {
+int dist_rccl_perform(amg_ctx* c, DistState* d, const amg_xfer& x) {
   hipStream_t st = c->stream;
   if (x.kind == AMG_XFER_ALL_GATHER) {
     NCCLCHK(g_rccl.AllGather(x.send, x.recv, (size_t)x.count * x.elem_bytes, ncclChar, d->comm, st));
@@ -641,7 +639,7 @@ static int rccl_perform(amg_ctx* c, DistState* d, const amg_xfer& x) {
 
 extern "C" int amg_dist_merge(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min_edge_cov) {
   NEED_CTX(c);
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   if ((d->world > 1 || d->always_exchange) && !d->comm)
     return amg_fail(AMG_E_STATE, "amg_dist_init first (or drive the exchanges yourself: amg_dist_merge_begin / _next)");
   AMGCHK(amg_dist_merge_begin(c, k, min_node_cov, min_edge_cov));
@@ -649,7 +647,7 @@ extern "C" int amg_dist_merge(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint
     amg_xfer x;
     const int r = amg_dist_merge_next(c, &x);
     if (r <= 0) return r;
-    const int e = rccl_perform(c, d, x);
+    const int e = dist_rccl_perform(c, d, x);
     if (e != AMG_OK) {
       d->state = S_IDLE;
       return e;
@@ -657,14 +655,49 @@ extern "C" int amg_dist_merge(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint
   }
 }
 
-// ---- emulated ranks: the ctxs of one process, one device; the exchanges are device copies
+// ---- emulated ranks: the ctxs of one process, one device; the exchanges are device copies (the merge's and the walks')
+int dist_local_exchange(amg_ctx* const* ctxs, int world, const amg_xfer* xs) {
+  for (int r = 0; r < world; ++r) HIPCHK(hipStreamSynchronize(ctxs[r]->stream));
+  hipStream_t st = ctxs[0]->stream;
+  for (int r = 1; r < world; ++r)
+    if (xs[r].kind != xs[0].kind || xs[r].elem_bytes != xs[0].elem_bytes)
+      return amg_fail(AMG_E_DIST, "emulated ranks ask for different exchanges");
+  const size_t eb = (size_t)xs[0].elem_bytes;
+  if (xs[0].kind == AMG_XFER_ALL_GATHER) {
+    for (int dst = 0; dst < world; ++dst)
+      for (int src = 0; src < world; ++src) {
+        if (xs[src].count != xs[0].count) return amg_fail(AMG_E_DIST, "all-gather sizes differ");
+        if (xs[src].count)
+          HIPCHK(hipMemcpyAsync(static_cast<char*>(xs[dst].recv) + (size_t)src * xs[0].count * eb, xs[src].send,
+                                (size_t)xs[0].count * eb, hipMemcpyDeviceToDevice, st));
+      }
+  } else {
+    for (int dst = 0; dst < world; ++dst) {
+      size_t ro = 0;
+      for (int src = 0; src < world; ++src) {
+        size_t so = 0;
+        for (int p = 0; p < dst; ++p) so += (size_t)xs[src].send_counts[p] * eb;
+        const size_t bytes = (size_t)xs[src].send_counts[dst] * eb;
+        if (xs[dst].recv_counts[src] != xs[src].send_counts[dst])
+          return amg_fail(AMG_E_DIST, "all-to-all counts of ranks %d and %d disagree", src, dst);
+        if (bytes)
+          HIPCHK(hipMemcpyAsync(static_cast<char*>(xs[dst].recv) + ro, static_cast<const char*>(xs[src].send) + so, bytes,
+                                hipMemcpyDeviceToDevice, st));
+        ro += bytes;
+      }
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return AMG_OK;
+}
+
 extern "C" int amg_dist_merge_local(amg_ctx* const* ctxs, int32_t world, int32_t k, uint32_t min_node_cov,
                                     uint32_t min_edge_cov) {
   if (!ctxs || world < 1) return amg_fail(AMG_E_ARG, "bad ctx list");
   for (int r = 0; r < world; ++r) {
     if (!ctxs[r]) return amg_fail(AMG_E_ARG, "null ctx");
     if (ctxs[r]->device != ctxs[0]->device) return amg_fail(AMG_E_ARG, "emulated ranks share one device");
-    DistState* d = dm(ctxs[r]);
+    DistState* d = dist_state(ctxs[r]);
     if (d->world != world || d->rank != r || d->comm) AMGCHK(set_world(ctxs[r], r, world));
     AMGCHK(amg_dist_merge_begin(ctxs[r], k, min_node_cov, min_edge_cov));
   }
@@ -672,7 +705,7 @@ extern "C" int amg_dist_merge_local(amg_ctx* const* ctxs, int32_t world, int32_t
   std::vector<amg_xfer> xs(world);
   auto abandon = [&](int ret) {
     const std::string msg = g_amg_err;
-    for (int r = 0; r < world; ++r) dm(ctxs[r])->state = S_IDLE;
+    for (int r = 0; r < world; ++r) dist_state(ctxs[r])->state = S_IDLE;
     g_amg_err = msg;
     return ret;
   };
@@ -694,44 +727,15 @@ extern "C" int amg_dist_merge_local(amg_ctx* const* ctxs, int32_t world, int32_t
     }
     if (done == world) return AMG_OK;
     if (pending != world) return abandon(amg_fail(AMG_E_DIST, "emulated ranks fell out of step"));
-    for (int r = 0; r < world; ++r) HIPCHK(hipStreamSynchronize(ctxs[r]->stream));
-    hipStream_t st = ctxs[0]->stream;
-    for (int r = 1; r < world; ++r)
-      if (xs[r].kind != xs[0].kind || xs[r].elem_bytes != xs[0].elem_bytes)
-        return abandon(amg_fail(AMG_E_DIST, "emulated ranks ask for different exchanges"));
-    const size_t eb = (size_t)xs[0].elem_bytes;
-    if (xs[0].kind == AMG_XFER_ALL_GATHER) {
-      for (int dst = 0; dst < world; ++dst)
-        for (int src = 0; src < world; ++src) {
-          if (xs[src].count != xs[0].count) return abandon(amg_fail(AMG_E_DIST, "all-gather sizes differ"));
-          if (xs[src].count)
-            HIPCHK(hipMemcpyAsync(static_cast<char*>(xs[dst].recv) + (size_t)src * xs[0].count * eb, xs[src].send,
-                                  (size_t)xs[0].count * eb, hipMemcpyDeviceToDevice, st));
-        }
-    } else {
-      for (int dst = 0; dst < world; ++dst) {
-        size_t ro = 0;
-        for (int src = 0; src < world; ++src) {
-          size_t so = 0;
-          for (int p = 0; p < dst; ++p) so += (size_t)xs[src].send_counts[p] * eb;
-          const size_t bytes = (size_t)xs[src].send_counts[dst] * eb;
-          if (xs[dst].recv_counts[src] != xs[src].send_counts[dst])
-            return abandon(amg_fail(AMG_E_DIST, "all-to-all counts of ranks %d and %d disagree", src, dst));
-          if (bytes)
-            HIPCHK(hipMemcpyAsync(static_cast<char*>(xs[dst].recv) + ro, static_cast<const char*>(xs[src].send) + so, bytes,
-                                  hipMemcpyDeviceToDevice, st));
-          ro += bytes;
-        }
-      }
-    }
-    HIPCHK(hipStreamSynchronize(st));
+    const int e = dist_local_exchange(ctxs, world, xs.data());
+    if (e != AMG_OK) return abandon(e);
   }
 }
 
 // out[i]: the statistic DistStat i (amg_dist.h), since the last reset
 extern "C" int amg_dist_stats(amg_ctx* c, int64_t* out, int32_t reset) {
   if (!c) return amg_fail(AMG_E_ARG, "null ctx");
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   if (out)
     for (int i = 0; i < DS_N; ++i) out[i] = d->st[i];
   if (reset)
@@ -743,7 +747,7 @@ extern "C" int amg_dist_stats(amg_ctx* c, int64_t* out, int32_t reset) {
 // synchronises the stream around every phase): names[i] points at static strings; returns the number of phases
 extern "C" int amg_dist_phase_ms(amg_ctx* c, int32_t on, const char** names, double* ms, int32_t cap) {
   if (!c) return amg_fail(AMG_E_ARG, "null ctx");
-  DistState* d = dm(c);
+  DistState* d = dist_state(c);
   int n = 0;
   for (int i = 0; i < 2 * S_N; ++i) {
     if (!kPhaseNames[i][0]) continue;

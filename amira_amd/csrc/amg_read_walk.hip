@@ -13,6 +13,7 @@
 //   C  n_reads[c] = reads with a live AMR window on a node of component c (a read counts once per component),
 //                   n_long[c] = those of them with at least min_genes genes
 #include "amg_device.h"
+#include "amg_read_walk.h"
 
 #define RW_READS_PER_WAVE 8  // as k_mask_reads (amg_filter.hip), and for its reason: see walk_reads
 #define RW_WAVES 4
@@ -23,7 +24,6 @@
 // RW_FLAG_WORDS_BUDGET: 20 480 genes = 2.5 KB, copied once per workgroup, i.e. once per n_reads / RW_MAX_BLOCKS reads.
 #define RW_FLAG_WORDS_MAX 4096
 #define RW_FLAG_WORDS_BUDGET 640
-#define RW_MAX_LENGTHS 16  // read lengths one amg_depth_by_length call answers for
 #define RW_CACHE_SLOTS 256  // LDS slots in which a workgroup sums up the components of C before it touches global memory
 
 struct RwArgs {
@@ -359,13 +359,15 @@ struct CompUse {
 };
 
 // ------------------------------------------------------------------ host side
-// A graph made by amg_dist_merge* has the nodes of all ranks' reads and the windows of this rank's reads alone
+// A graph made by amg_dist_merge* has the nodes of all ranks' reads and the windows of this rank's reads alone: the
+// single-GPU calls would answer for a shard, the collective (amg_dist_walk*, amg_dist_walk.hip) answers for all reads
 #define NEED_ALL_READS(c, what)                                                                                         \
   do {                                                                                                                  \
     NEED_BUILT(c);                                                                                                      \
     if ((c)->dist_mode)                                                                                                 \
       return amg_fail(AMG_E_STATE, what ": the graph came from a merged build (amg_dist_merge*), this ctx holds only "  \
-                                        "its own shard of the reads; sums across ranks are not made");                  \
+                                        "its own shard of the reads; sums across ranks are not made here "              \
+                                        "(the collective: amg_dist_walk*)");                                            \
   } while (0)
 
 static RwArgs rw_args(amg_ctx* c, const unsigned int* flag_bits, int flag_words) {
@@ -402,18 +404,14 @@ static int rw_upload_flags(amg_ctx* c, const uint8_t* gene_flags, std::vector<un
   return AMG_OK;
 }
 
-extern "C" int amg_depth_by_length(amg_ctx* c, const int32_t* min_genes, int32_t n, int64_t* pairs, int64_t* n_alive) {
-  NEED_ALL_READS(c, "amg_depth_by_length");
-  if (!min_genes || !pairs || !n_alive) return amg_fail(AMG_E_ARG, "null argument");
-  if (n < 1 || n > RW_MAX_LENGTHS) return amg_fail(AMG_E_ARG, "n must be in [1, %d]", RW_MAX_LENGTHS);
-  stages_reset(c);
+
+// ---- the local phases: the walks over the reads THIS ctx holds.  The single-GPU entry points below are a local phase
+// and a read-back; the walks across ranks (amg_dist_walk.hip) put an exchange and a fold between the two.
+int rw_depth_local(amg_ctx* c, const int32_t* min_genes, int32_t n, unsigned long long* out) {
   stage_begin(c, "depth");
-  const size_t out_bytes = (RW_MAX_LENGTHS + 1) * sizeof(unsigned long long);
-  AMGCHK(c->s4.ensure(out_bytes));
-  unsigned long long* out = c->s4.as<unsigned long long>();  // pairs[16], then the alive nodes
   {
     ClearList cl;
-    cl.add(out, out_bytes);
+    cl.add(out, RW_DEPTH_WORDS * sizeof(unsigned long long));
     AMGCHK(clear_many(c, cl));
   }
   DepthUse use;
@@ -425,9 +423,68 @@ extern "C" int amg_depth_by_length(amg_ctx* c, const int32_t* min_genes, int32_t
     hipLaunchKernelGGL(k_rw_count_alive, dim3(nblk(c->n_nodes, 2048) < 256u ? nblk(c->n_nodes, 2048) : 256u), dim3(256), 0,
                        c->stream, c->node_alive.as<unsigned char>(), c->n_nodes, out + RW_MAX_LENGTHS);
   stage_end(c);
-  unsigned long long host[RW_MAX_LENGTHS + 1];
+  return AMG_OK;
+}
+
+int rw_keep_local(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned int>* words) {
+  const long long D = c->n_nodes;
+  AMGCHK(rw_upload_flags(c, gene_flags, words));
+  AMGCHK(c->s0.ensure((size_t)D + 8));
+  AMGCHK(c->s1.ensure((size_t)c->n_reads + 8));
+  AMGCHK(c->s4.ensure((size_t)D + 8));
+  {
+    ClearList cl;
+    cl.add(c->s0.p, (size_t)D + 8);
+    cl.add(c->s4.p, (size_t)D + 8);
+    AMGCHK(clear_many(c, cl));
+  }
+  if (c->n_reads > 0) {
+    HitUse hit;
+    hit.hit = c->s1.as<unsigned char>();
+    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words->size()), hit);
+    KeepUse keep;
+    keep.hit = c->s1.as<unsigned char>();
+    keep.keep = c->s4.as<unsigned char>();
+    rw_launch(c, rw_args(c, nullptr, 0), keep);
+  }
+  return AMG_OK;
+}
+
+int rw_comp_local(amg_ctx* c, const uint8_t* gene_flags, int32_t min_genes, std::vector<unsigned int>* words) {
+  const long long nc = c->n_components;
+  stage_begin(c, "amr_reads");
+  AMGCHK(rw_upload_flags(c, gene_flags, words));
+  const size_t out_bytes = 2 * (size_t)nc * sizeof(unsigned long long);
+  AMGCHK(c->s4.ensure(out_bytes));
+  {
+    ClearList cl;
+    cl.add(c->s4.p, out_bytes);
+    AMGCHK(clear_many(c, cl));
+  }
+  if (c->n_reads > 0) {
+    CompUse use;
+    use.n_reads = c->s4.as<unsigned long long>();
+    use.n_long = use.n_reads + nc;
+    use.n_comp = (int)nc;
+    use.min_genes = min_genes;
+    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words->size()), use);
+  }
+  stage_end(c);
+  return AMG_OK;
+}
+
+// ------------------------------------------------------------------ the single-GPU entry points
+extern "C" int amg_depth_by_length(amg_ctx* c, const int32_t* min_genes, int32_t n, int64_t* pairs, int64_t* n_alive) {
+  NEED_ALL_READS(c, "amg_depth_by_length");
+  if (!min_genes || !pairs || !n_alive) return amg_fail(AMG_E_ARG, "null argument");
+  if (n < 1 || n > RW_MAX_LENGTHS) return amg_fail(AMG_E_ARG, "n must be in [1, %d]", RW_MAX_LENGTHS);
+  stages_reset(c);
+  AMGCHK(c->s4.ensure(RW_DEPTH_WORDS * sizeof(unsigned long long)));
+  unsigned long long* out = c->s4.as<unsigned long long>();
+  AMGCHK(rw_depth_local(c, min_genes, n, out));
+  unsigned long long host[RW_DEPTH_WORDS];
   FetchList l;
-  l.add_words(out, RW_MAX_LENGTHS + 1);
+  l.add_words(out, RW_DEPTH_WORDS);
   AMGCHK(fetch(c, l, host));
   for (int j = 0; j < n; ++j) pairs[j] = (int64_t)host[j];
   *n_alive = (int64_t)host[RW_MAX_LENGTHS];
@@ -443,25 +500,7 @@ extern "C" int amg_remove_non_amr_nodes(amg_ctx* c, const uint8_t* gene_flags, i
   stages_reset(c);
   stage_begin(c, "amr_trim");
   std::vector<unsigned int> words;
-  AMGCHK(rw_upload_flags(c, gene_flags, &words));
-  AMGCHK(c->s0.ensure((size_t)D + 8));
-  AMGCHK(c->s1.ensure((size_t)c->n_reads + 8));
-  AMGCHK(c->s4.ensure((size_t)D + 8));
-  {
-    ClearList cl;
-    cl.add(c->s0.p, (size_t)D + 8);
-    cl.add(c->s4.p, (size_t)D + 8);
-    AMGCHK(clear_many(c, cl));
-  }
-  if (c->n_reads > 0) {
-    HitUse hit;
-    hit.hit = c->s1.as<unsigned char>();
-    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words.size()), hit);
-    KeepUse keep;
-    keep.hit = c->s1.as<unsigned char>();
-    keep.keep = c->s4.as<unsigned char>();
-    rw_launch(c, rw_args(c, nullptr, 0), keep);
-  }
+  AMGCHK(rw_keep_local(c, gene_flags, &words));
   hipLaunchKernelGGL(k_rw_kill_unkept, dim3(nblk(D, 256)), dim3(256), 0, c->stream, c->node_alive.as<unsigned char>(),
                      c->s4.as<unsigned char>(), D, c->s0.as<unsigned char>());
   c->have_corrected = false;
@@ -481,25 +520,8 @@ extern "C" int amg_component_amr_reads(amg_ctx* c, const uint8_t* gene_flags, in
   if (!gene_flags || !n_reads || !n_long) return amg_fail(AMG_E_ARG, "null argument");
   if (cap < nc) return amg_fail(AMG_E_ARG, "room for %lld components, the graph has %lld", (long long)cap, nc);
   if (nc == 0) return AMG_OK;
-  stage_begin(c, "amr_reads");
   std::vector<unsigned int> words;
-  AMGCHK(rw_upload_flags(c, gene_flags, &words));
-  const size_t out_bytes = 2 * (size_t)nc * sizeof(unsigned long long);
-  AMGCHK(c->s4.ensure(out_bytes));
-  {
-    ClearList cl;
-    cl.add(c->s4.p, out_bytes);
-    AMGCHK(clear_many(c, cl));
-  }
-  if (c->n_reads > 0) {
-    CompUse use;
-    use.n_reads = c->s4.as<unsigned long long>();
-    use.n_long = use.n_reads + nc;
-    use.n_comp = (int)nc;
-    use.min_genes = min_genes;
-    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words.size()), use);
-  }
-  stage_end(c);
+  AMGCHK(rw_comp_local(c, gene_flags, min_genes, &words));
   HIPCHK(hipMemcpyAsync(n_reads, c->s4.p, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(n_long, c->s4.as<unsigned long long>() + nc, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost,
                         c->stream));

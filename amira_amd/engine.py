@@ -541,6 +541,53 @@ class Engine:
         handles = (C.c_void_p * n)(*[e._h for e in engines])
         check(_ffi.lib.amg_dist_merge_local(handles, n, int(k), max(int(min_node_cov), 1), max(int(min_edge_cov), 1)))
 
+    # ---- the read walks on a merged graph, over the reads of all ranks (include/amg.h amg_dist_walk*; which: _ffi.WALK_*)
+    def _walk_args(self, which, flags, min_genes):
+        """(flags, min_genes, n, room for the answer) as amg_dist_walk* take them"""
+        flags = None if which == _ffi.WALK_DEPTH else self._gene_flags(flags)
+        if which == _ffi.WALK_AMR_TRIM:
+            return flags, None, 0, 1
+        mg = np.ascontiguousarray(np.atleast_1d(min_genes), dtype=np.int32)
+        room = len(mg) + 1 if which == _ffi.WALK_DEPTH else 2 * max(self.graph_sizes()[0], 1)
+        return flags, mg, len(mg), room
+
+    def dist_walk(self, which, flags=None, min_genes=None):
+        """collective over RCCL: the walk's answer as int64 values (include/amg.h for their layout)"""
+        flags, mg, n, room = self._walk_args(which, flags, min_genes)
+        out, n_out = np.empty(room, np.int64), C.c_int64(0)
+        check(_ffi.lib.amg_dist_walk(self._h, int(which), ptr(flags), ptr(mg), n, ptr(out), room, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    @staticmethod
+    def dist_walk_local(engines, which, flags=None, min_genes=None):
+        """the same between len(engines) EMULATED ranks (the engines of dist_merge_local, in rank order)"""
+        flags, mg, n, room = engines[0]._walk_args(which, flags, min_genes)
+        handles = (C.c_void_p * len(engines))(*[e._h for e in engines])
+        out, n_out = np.empty(room, np.int64), C.c_int64(0)
+        check(_ffi.lib.amg_dist_walk_local(handles, len(engines), int(which), ptr(flags), ptr(mg), n, ptr(out), room,
+                                           C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def dist_walk_begin(self, which, flags=None, min_genes=None):
+        """the same with the exchanges left to the caller: then dist_walk_next until it returns None, then dist_walk_result"""
+        flags, mg, n, _ = self._walk_args(which, flags, min_genes)
+        check(_ffi.lib.amg_dist_walk_begin(self._h, int(which), ptr(flags), ptr(mg), n))
+
+    def dist_walk_next(self):
+        """None when the walk is complete, else the exchange to perform before the next call (an _ffi.Xfer)"""
+        x = _ffi.Xfer()
+        rc = _ffi.lib.amg_dist_walk_next(self._h, C.byref(x))
+        if rc < 0:
+            check(rc)
+        return x if rc == 1 else None
+
+    def dist_walk_result(self):
+        n_out = C.c_int64(0)
+        _ffi.lib.amg_dist_walk_result(self._h, None, 0, C.byref(n_out))   # (the size; AMG_E_ARG unless the answer is empty)
+        out = np.empty(max(n_out.value, 1), np.int64)
+        check(_ffi.lib.amg_dist_walk_result(self._h, ptr(out), len(out), C.byref(n_out)))
+        return out[:n_out.value].copy()
+
     def dist_finalize(self):
         check(_ffi.lib.amg_dist_finalize(self._h))
 

@@ -189,6 +189,21 @@ def iterative_bubble_popping(new_annotatedReads, new_gene_position_dict, cleanin
     return new_annotatedReads, new_gene_position_dict
 
 
+def mean_of_ints(total, n):
+    """statistics.mean of n ints that sum to total, as graph_utils.py:299-313 takes it per k: the int when the division
+    is exact, else the correctly rounded float; 0 for no node at all (the drivers' convention)"""
+    total, n = int(total), int(n)
+    if n == 0:
+        return 0
+    return total // n if total % n == 0 else float(Fraction(total, n))
+
+
+def components_valid(n_reads, n_long):
+    """choose_kmer_size's test of one k (graph_utils.py:258-296): in every component that has reads through AMR nodes
+    at all, at least 80 % of them are long (the reference's float expression)"""
+    return all(n == 0 or m / n >= 0.8 for n, m in zip(n_reads, n_long))
+
+
 def choose_kmer_size(overall_mean_node_coverage, new_annotatedReads, cores, new_gene_position_dict,
                      sample_genesOfInterest):
     """largest odd k in 3..15 such that, in every component, >= 80 % of the reads through
@@ -205,7 +220,7 @@ def choose_kmer_size(overall_mean_node_coverage, new_annotatedReads, cores, new_
             # per component, the reads through its AMR nodes and those of them with 2k - 1 genes: one walk over the
             # reads on the device (amg_component_amr_reads) — no Node object, hash or view is made
             n_reads, n_long = graph._engine.component_amr_reads(flags, 2 * k - 1)
-            if all(n == 0 or m / n >= 0.8 for n, m in zip(n_reads.tolist(), n_long.tolist())):
+            if components_valid(n_reads.tolist(), n_long.tolist()):
                 geneMer_size = k
             else:
                 break
@@ -222,11 +237,7 @@ def get_overall_mean_node_coverages(graph):
     if not graph._host_edits:
         ks = list(range(3, 16, 2))
         pairs, n_alive = graph._engine.depth_by_length(ks)
-        out = {}
-        for k, p in zip(ks, pairs.tolist()):
-            # statistics.mean of a list of ints: the int when the division is exact, else the correctly rounded float
-            out[k] = 0 if n_alive == 0 else (p // n_alive if p % n_alive == 0 else float(Fraction(p, n_alive)))
-        return out
+        return {k: mean_of_ints(p, n_alive) for k, p in zip(ks, pairs.tolist())}
     off, idx = graph._engine.node_reads()
     alive = graph._engine.nodes()["alive"] != 0
     read_len = np.diff(graph._read_off)

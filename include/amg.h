@@ -210,7 +210,8 @@ int amg_get_reads_to_correct(amg_ctx* ctx, uint8_t* flags);
  *      per-window node ids on the device (amira_amd/csrc/amg_read_walk.hip).  A window is LIVE when its node id is >= 0
  *      and the node alive.  gene_flags: two_v / 2 HOST bytes indexed by gene rank, non-zero = gene of interest; a
  *      window is an AMR window when one of its k genes is flagged (== its node's canonical gene-mer holds the gene).
- *      AMG_E_STATE on a graph made by amg_dist_merge* (the ctx holds only its shard of the reads). -------------- */
+ *      AMG_E_STATE on a graph made by amg_dist_merge* (the ctx holds only its shard of the reads): there the collective
+ *      amg_dist_walk* (multi-GPU, below) answers the same three questions over the reads of all ranks. ------------ */
 /* get_overall_mean_node_coverages (graph_utils.py:299-313): pairs[j] = distinct (read, node) pairs with a live window
  * of the read on the node, over the reads of at least min_genes[j] genes (a node a read visits twice counts once,
  * construct_node.py:64-67); *n_alive = alive nodes; the mean over nodes is pairs[j] / n_alive.  n in [1, 16]. */
@@ -431,7 +432,34 @@ int amg_dist_merge_local(amg_ctx* const* ctxs, int32_t world, int32_t k, uint32_
  * (what a host-staged transport needs around its collectives) */
 int amg_copy_d2h(amg_ctx* ctx, const void* device_ptr, void* host_ptr, int64_t bytes);
 int amg_copy_h2d(amg_ctx* ctx, void* device_ptr, const void* host_ptr, int64_t bytes);
-/* counters of the ctx's merged builds since the last reset: out[0] host waits on exchanged counts, [1] exchanges,
+/* ---- the read walks (above) on a merged graph, over the reads of ALL ranks: each rank walks its own reads, the ranks
+ *      exchange their parts in all-gathers, every rank folds them (amira_amd/csrc/amg_dist_walk.hip).
+ *      Collective: every rank calls with the same arguments, on the graph its last amg_dist_merge* left.  gene_flags and
+ *      min_genes as in the single-GPU calls: AMG_WALK_DEPTH takes min_genes[n], n in [1, 16]; AMG_WALK_AMR_TRIM takes
+ *      gene_flags (min_genes and n are not read); AMG_WALK_COMPONENT_READS takes gene_flags and one min_genes value, n = 1.
+ *      The first exchange carries a header of every rank {walk, the code of its local phase, k, n, nodes, components, a
+ *      hash of the arguments, two_v}: when a rank failed or any field differs EVERY rank returns AMG_E_DIST, no node has
+ *      been removed, and the ctx is ready for the next call.  Exchanges: one for the depth, two for the others.
+ *      The answer, in `out` (*n_out values; cap < *n_out is AMG_E_ARG with *n_out written and nothing else):
+ *        AMG_WALK_DEPTH            pairs[0 .. n) summed over the ranks, then the alive nodes
+ *        AMG_WALK_AMR_TRIM         the nodes removed: every rank ends with the graph amg_remove_non_amr_nodes leaves on the
+ *                                  unsharded reads, with its own reads' windows masked and its own reads marked for correction
+ *        AMG_WALK_COMPONENT_READS  n_reads[0 .. nc), then n_long[0 .. nc) of amg_component_amr_reads, nc = components
+ *      AMG_E_STATE: the graph is not from a merged build (use the single-GPU call), or a merged build or another walk is
+ *      under way on the ctx.
+ *      amg_dist_walk performs the exchanges over RCCL (amg_dist_init), amg_dist_walk_local between emulated ranks (the
+ *      ctxs of amg_dist_merge_local, in rank order; the one answer is written once), and amg_dist_walk_begin / _next /
+ *      _result leave them to the caller as amg_dist_merge_begin / _next do: 1 = perform *out on every rank and call again,
+ *      0 = done, fetch the answer with amg_dist_walk_result (any number of times until the next walk begins). --------- */
+enum { AMG_WALK_DEPTH = 1, AMG_WALK_AMR_TRIM = 2, AMG_WALK_COMPONENT_READS = 3 };
+int amg_dist_walk(amg_ctx* ctx, int32_t which, const uint8_t* gene_flags, const int32_t* min_genes, int32_t n, int64_t* out,
+                  int64_t cap, int64_t* n_out);
+int amg_dist_walk_local(amg_ctx* const* ctxs, int32_t world, int32_t which, const uint8_t* gene_flags,
+                        const int32_t* min_genes, int32_t n, int64_t* out, int64_t cap, int64_t* n_out);
+int amg_dist_walk_begin(amg_ctx* ctx, int32_t which, const uint8_t* gene_flags, const int32_t* min_genes, int32_t n);
+int amg_dist_walk_next(amg_ctx* ctx, amg_xfer* out);
+int amg_dist_walk_result(amg_ctx* ctx, int64_t* out, int64_t cap, int64_t* n_out);
+/* counters of the ctx's merged builds and walks across ranks since the last reset: out[0] host waits on exchanged counts, [1] exchanges,
  * [2] most bytes of records sent to ONE peer, [3] the same of replies, [4] bytes contributed to the all-gathers,
  * [5] builds repeated after a merge-key collision, [6] bytes of records sent to all peers, [7] builds made from the
  * previous merged graph's live part (no rank had re-threaded a read: two exchanges instead of ten) */
