@@ -2,8 +2,11 @@
 // units have to agree on, and the host's view of ONE amg_correct_reads call (switches, scratch plan, counts read
 // back) with the stage functions that work on it.
 //   amg_correct.hip         classify, shape, pack, and amg_correct_reads itself (the pipeline is described there)
-//   amg_correct_gapped.hip  re-threading of the reads with None runs      (stage correct_gapped)
-//   amg_gap_memo.hip        the path memo's search, a lane per question   (stage correct_gapped)
+//   amg_correct_gapped.hip  re-threading of the reads with None runs      (stage correct_gapped: its driver)
+//   amg_gap_memo.hip        the path memo: every question of the None runs answered once
+//   amg_gap_lean.hip        sixteen lanes per read: the reads whose every question has one answer
+//   amg_gap_fast.hip        a wave per read, staged in LDS
+//   amg_gap_general.hip     a thread per read, global pool and scratch: what exceeds the LDS capacities
 //   amg_correct_nw.hip      position carry-over of the re-threaded reads  (stage correct_positions)
 //   amg_nw_probe.hip        amg_nw_probe: that stage alone on host arrays (test entry)
 //   amg_corrected.hip       the corrected set at the boundary (it gathers positions through CorrArgs' pools)
@@ -89,7 +92,7 @@ __device__ __forceinline__ int wave_prefix_max(int g, const int id) {
   return g;
 }
 
-// ---- re-threading (amg_correct_gapped.hip)
+// ---- re-threading (amg_correct_gapped.hip and the amg_gap_* units)
 // what the wave-per-read kernel needs to start on gapped read gi, in one 32-byte record
 // (written by k_scatter_gapped) instead of a chain of dependent per-read loads
 struct __attribute__((aligned(16))) GapRec {
@@ -297,8 +300,6 @@ static void fill_pos_args(amg_ctx* c, CorrArgs& a) {
 }
 
 // ---- the steps that live with their kernels
-// k_corr_classify alone (it lives in amg_correct_gapped.hip, see there; its step is amg_correct.hip's)
-void corr_classify_launch(amg_ctx* c, const CorrArgs& a);
 // stage correct_gapped: a has tmp_tok; writes the staged genes, new_len and final_cls of the gapped reads
 int corr_gapped(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, CorrCounts& n);
 // inside the shape step: sizes of the carry-over's scratch and products, their totals appended to `shape`
@@ -309,11 +310,21 @@ int corr_grow_pos_pools(amg_ctx* c, const CorrCounts& n);
 int corr_positions(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrArgs& a, const CorrCounts& n,
                    unsigned char* route = nullptr);  // route: NwArgs::route (amg_nw_probe only)
 
-// the path memo's search a lane per question (amg_gap_memo.hip): for the k whose search fits its stack, else k_gap_dfs
-bool gap_dfs_lanes_fits(int k);
-void gap_dfs_lanes_launch(amg_ctx* c, const int* qlist, long long n_queries, const unsigned long long* qtab,
-                          unsigned long long* pool_used, unsigned long long pool_cap, int* qpool, int4* qres,
-                          int* qgene);
+// ---- the parts of stage correct_gapped, each with its kernels (corr_gapped, amg_correct_gapped.hip, runs them)
+// amg_gap_memo.hip: the questions of the None runs entered and answered; *gq: per-read question slots (nullptr: no memo)
+int corr_gap_memo(amg_ctx* c, const CorrSwitches& sw, const CorrArgs& a, CorrCounts& n, const int** gq);
+// amg_gap_lean.hip: k_corr_gapped_lean over every gapped read; qgene: the memo's genes, left: a GL_* code per read
+void corr_gapped_lean_launch(amg_ctx* c, const GapArgs& G, const int* qgene, unsigned char* left);
+// amg_gap_fast.hip: k_corr_gapped_fast; left == nullptr: every gapped read, else the reads flagged there
+void corr_gapped_fast_launch(amg_ctx* c, const GapArgs& G, const unsigned char* left);
+// amg_gap_general.hip: room for k_corr_gapped (candidate scratch, need_slow, the first path pool), then the kernel
+// over the reads flagged in need_slow; it grows the pool (G.pool, G.pool_cap) and runs again while one overflows it
+struct GeneralRoom {
+  unsigned int cand_stride;
+  unsigned long long pool_cap;
+};
+int corr_general_room(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrCounts& n, GeneralRoom& room);
+int corr_gapped_general(amg_ctx* c, const CorrScratch& S, GapArgs& G, CorrCounts& n);
 
 // ---- route report (amg_correct_routes.hip), only with CorrSwitches::routes: small tally kernels behind the steps
 int routes_begin(amg_ctx* c);

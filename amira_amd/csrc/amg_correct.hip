@@ -7,10 +7,11 @@
 //              [start, end] (find_read_boundaries :1153-1164), None runs inside (identify_path_terminals :1375-1386);
 //              unmarked reads are copies, reads that only lost their ends are slices ([start : end + k], :1277-1285);
 //              reads with None runs are RC_GAPPED and get a staging bound.  One scan pair: staging offsets, gapped list.
-//   gapped     (amg_correct_gapped.hip, after the live adjacency is up to date)  k_scatter_gapped lists the gapped reads
-//              with a start record each.  Path memo: k_gap_queries enters every None run's (start, direction, end)
-//              question into a table, k_gap_dfs answers each once (new_find_paths_between_nodes :2292-2342, a wave
-//              per question).  Then per read the cartesian product of the replacements (insert_elements :1166-1203),
+//   gapped     (amg_correct_gapped.hip with the amg_gap_* units, after the live adjacency is up to date)
+//              k_scatter_gapped lists the gapped reads with a start record each.  Path memo (amg_gap_memo.hip):
+//              k_gap_queries enters every None run's (start, direction, end) question into a table, k_gap_dfs_lanes or
+//              k_gap_dfs answers each once (new_find_paths_between_nodes :2292-2342, a lane or a wave per question).
+//              Then per read the cartesian product of the replacements (insert_elements :1166-1203),
 //              best candidate by shared genes, then mean coverage (:1297-1310), genes via get_annotation_for_read
 //              (:1331-1373): k_corr_gapped_lean, sixteen lanes per read, for reads whose questions have one answer
 //              each -> k_corr_gapped_fast, a wave per read in LDS, for what that left -> k_corr_gapped, a thread per
@@ -44,6 +45,138 @@ __global__ __launch_bounds__(256) void k_count_alive(const unsigned char* __rest
   __syncthreads();
   if (threadIdx.x == 0 && (s_part[0] | s_part[1] | s_part[2] | s_part[3]))
     atomicAdd(out, (unsigned long long)s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+}
+
+// ---- classification.
+// One wave classifies 64 consecutive reads.  Lane l owns read l: its offsets, fix flag and results are loaded and
+// stored coalesced, one read per lane.  What needs the read's windows — which are live — is a 64-bit mask per read:
+// the wave loads the windows of one flagged read at a time (lanes = windows, four reads in flight), ballots, and
+// hands the mask to the owning lane; everything else is bit arithmetic on that mask.  (A wave per four reads
+// stored every result with its own one-lane instruction: ~8 vector-memory instructions per read.)
+__global__ __launch_bounds__(256) void k_corr_classify(CorrArgs a) {
+  const long long rbase = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * CLS_READS;
+  if (rbase >= a.n_reads) return;
+  const int lane = threadIdx.x & 63;
+  const long long r = rbase + lane;
+  const bool have = r < a.n_reads;
+  const long long t0 = have ? a.read_off[r] : 0;
+  const long long n = have ? (a.read_off[r + 1] - t0) - a.k + 1 : 0;  // windows; L = n + k - 1
+  const bool look = have && n > 0 && a.read_fix[r] != 0;
+  // live-window masks of the flagged reads with <= 64 windows
+  unsigned long long lv = 0;
+  unsigned long long todo = __ballot(look && n <= 64);
+  while (todo) {
+    int who[4];
+    long long tj[4];
+    int nj[4], v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      who[q] = todo ? __ffsll((long long)todo) - 1 : -1;
+      if (todo) todo &= todo - 1ull;
+      tj[q] = who[q] >= 0 ? bcast_i64(t0, who[q]) : 0;
+      nj[q] = who[q] >= 0 ? __builtin_amdgcn_readlane((int)n, who[q]) : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = lane < nj[q] ? a.tok_node[tj[q] + lane] : -1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned long long m = __ballot(v[q] >= 0);  // lanes >= n hold -1
+      if (lane == who[q]) lv = m;
+    }
+  }
+  long long first = n, last = -1;
+  unsigned int runs = 0, live = 0;
+  if (look && n <= 64) {
+    first = lv ? (long long)__ffsll((long long)lv) - 1 : n;
+    last = lv ? 63 - (long long)__clzll((long long)lv) : -1;
+    live = (unsigned int)__popcll(lv);
+    // a None run ends where the next window is live (windows past `last` are not live)
+    const unsigned long long inside =
+        lv ? ((last == 63 ? ~0ull : ((1ull << (last + 1)) - 1ull)) & ~((1ull << first) - 1ull)) : 0ull;
+    runs = (unsigned int)__popcll(~lv & inside & (lv >> 1));
+  }
+  // flagged reads longer than one wave: the wave walks each of them
+  unsigned long long big = __ballot(look && n > 64);
+  while (big) {
+    const int w = __ffsll((long long)big) - 1;
+    big &= big - 1ull;
+    const long long tw = bcast_i64(t0, w), nw = bcast_i64(n, w);
+    long long f = nw, l = -1;
+    for (long long i = lane; i < nw; i += 64)
+      if (a.tok_node[tw + i] >= 0) {
+        f = f < i ? f : i;
+        l = l > i ? l : i;
+      }
+    for (int d = 32; d > 0; d >>= 1) {
+      const long long f2 = __shfl_xor(f, d, 64), l2 = __shfl_xor(l, d, 64);
+      f = f < f2 ? f : f2;
+      l = l > l2 ? l : l2;
+    }
+    unsigned int ru = 0, li = 0;
+    if (l >= 0) {
+      for (long long i = f + lane; i <= l; i += 64) {
+        const bool none = a.tok_node[tw + i] < 0;
+        li += none ? 0u : 1u;
+        if (none && a.tok_node[tw + i + 1] >= 0) ++ru;
+      }
+      for (int d = 32; d > 0; d >>= 1) {
+        ru += __shfl_xor(ru, d, 64);
+        li += __shfl_xor(li, d, 64);
+      }
+    }
+    if (lane == w) {
+      first = f;
+      last = l;
+      runs = ru;
+      live = li;
+    }
+  }
+  const long long L = n + a.k - 1;
+  unsigned char cls;
+  int start = 0, end = -1;
+  unsigned int bound = 0;
+  unsigned int len_out = 0;  // genes of the corrected read, known here unless it has None runs
+  if (n <= 0) {
+    cls = RC_SKIP;  // no entry in _readNodes: correct_reads never sees the read (:1128)
+  } else if (!look) {
+    cls = RC_COPY;
+    len_out = (unsigned int)L;
+  } else if (last < 0) {
+    cls = RC_DROP;  // every node filtered: the read is dropped (:1141,:1150)
+  } else {
+    start = (int)first;
+    end = (int)last;
+    if (runs == 0) {
+      cls = RC_TRIM;
+      len_out = (unsigned int)(end - start + a.k);
+    } else {
+      cls = RC_GAPPED;
+      const unsigned int b1 = live + runs * (unsigned int)(2 * a.k) + (unsigned int)a.k;
+      bound = b1 > (unsigned int)L ? b1 : (unsigned int)L;  // may fall back to the original genes
+    }
+  }
+  if (have) {
+    a.cls[r] = cls;
+    a.cls_final[r] = cls;
+    a.r_start[r] = start;
+    a.r_end[r] = end;
+    a.bound[r] = bound;    // temp space: only re-threaded reads are staged
+    a.new_len[r] = len_out;
+    a.gflag[r] = cls == RC_GAPPED ? 1u : 0u;  // list of re-threaded reads (scan input)
+    a.lmask[r] = (cls == RC_GAPPED && n <= 64) ? lv : 0ull;
+  }
+  // largest staging bound of a re-threaded read and the number of None runs: one atomic per wave each (the maximum
+  // only when it raises a plain — possibly stale, never too large — read of it); lanes past the last read hold zeros
+  unsigned int mb = (have && cls == RC_GAPPED) ? bound : 0u;
+  unsigned int nr = (have && cls == RC_GAPPED) ? runs : 0u;
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned int o = (unsigned int)__shfl_xor((int)mb, d, 64);
+    mb = mb > o ? mb : o;
+    nr += (unsigned int)__shfl_xor((int)nr, d, 64);
+  }
+  if (lane == 0 && (unsigned long long)mb > *a.max_bound) atomicMax(a.max_bound, (unsigned long long)mb);
+  // (16 counter words 128 bytes apart: one word takes ~90 atomics per microsecond, a wave per 64 reads asks more)
+  if (lane == 0 && nr) atomicAdd(a.n_runs + 16 * (blockIdx.x & 15), (unsigned long long)nr);
 }
 
 // One wave packs 64 consecutive reads.  Lane l owns read l's record: where its genes come from (the read itself,
@@ -224,7 +357,7 @@ static int corr_classify(amg_ctx* c, const CorrScratch& S, const CorrArgs& a, Co
     cl.add(S.n_runs, (256 + 256 + 16) * sizeof(unsigned long long));
     AMGCHK(clear_many(c, cl));
   }
-  if (R > 0) corr_classify_launch(c, a);
+  if (R > 0) hipLaunchKernelGGL(k_corr_classify, dim3(nblk(R, 4 * CLS_READS)), dim3(256), 0, st, a);  // also new_len, flag, max
   // (for the next build's table: how many nodes are alive; rides along, read back with the pack step's words)
   if (S.count_alive)
     hipLaunchKernelGGL(k_count_alive, dim3(128), dim3(256), 0, st, c->node_alive.as<unsigned char>(), c->n_nodes,

@@ -1,7 +1,7 @@
 // amg_gap_search.h — what the units of the re-threading's path search share: the question key of the path memo, the
 // visitor that writes the paths of one None run on the wave-cooperative search (amg_wave_dfs.h), and the gene a node
-// spells in a direction.  Users: amg_correct_gapped.hip (k_gap_queries, k_gap_dfs, k_corr_gapped, k_corr_gapped_fast)
-// and amg_gap_memo.hip (k_gap_dfs_lanes).
+// spells in a direction, and the rule that ranks a read's candidates.  Users: amg_gap_memo.hip (k_gap_queries,
+// k_gap_dfs, k_gap_dfs_lanes), amg_gap_general.hip (k_corr_gapped) and amg_gap_fast.hip (k_corr_gapped_fast).
 #pragma once
 #include "amg_correct.h"
 #include "amg_wave_dfs.h"
@@ -56,4 +56,11 @@ __device__ __forceinline__ int dfs_paths_wave(const GView& g, int s, int sdir, i
 __device__ __forceinline__ unsigned long long gap_query_key(int s, int sdir, int e) {
   return (1ull << 63) | ((unsigned long long)(unsigned int)s << 32) | ((unsigned long long)(unsigned int)e << 1) |
          (sdir == 1 ? 1ull : 0ull);
+}
+
+// the rule that ranks candidates: strictly more shared genes, or equal and strictly higher mean coverage (:1301-1308;
+// csum / n against best_sum / best_len by exact cross-multiplication = the order of statistics.mean)
+__device__ __forceinline__ bool cand_better(int shared, unsigned long long csum, int n, int best_shared,
+                                            unsigned long long best_sum, unsigned long long best_len) {
+  return shared > best_shared || (shared == best_shared && csum * best_len > best_sum * (unsigned long long)n);
 }

@@ -297,7 +297,7 @@ struct amg_ctx {
   DevBuf s0, s1, s2, s3, s4, s5;  // general scratch arrays
   DevBuf nw_big;       // global scratch of the general position carry-over kernel (long reads)
   DevBuf gap_rec;      // per gapped read: the record k_corr_gapped_fast starts from
-  // path memo of the re-threading (amg_correct_gapped.hip: k_gap_queries / k_gap_dfs)
+  // path memo of the re-threading (amg_gap_memo.hip: k_gap_queries / k_gap_dfs)
   DevBuf gm_mask;      // uint64[n_reads]   live-window mask per read (k_corr_classify)
   DevBuf gm_tab;       // uint64[slots]     question table: (start node, direction, end node)
   DevBuf gm_res;       // int4  [slots]     per question {pool offset, ints, paths}

@@ -11,8 +11,8 @@
 //   WD_EXPAND   go on through the node's list,
 //   WD_RETREAT  this node ends the path (accepted or too long): back to the level before,
 //   WD_ABORT    the whole search ends here.
-// Users: the re-threading (amg_correct_gapped.hip: k_gap_dfs, k_corr_gapped_fast) and the junction search
-// (amg_bubbles.hip: k_bj_dfs).
+// Users: the re-threading (amg_gap_memo.hip: k_gap_dfs, k_gap_dfs_lanes; amg_gap_fast.hip: k_corr_gapped_fast) and the
+// junction search (amg_bubbles.hip: k_bj_dfs).
 #pragma once
 #include "amg_device.h"
 

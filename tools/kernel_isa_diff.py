@@ -9,7 +9,9 @@
 For every kernel symbol (.amdhsa_kernel NAME) in either directory it takes the text from the symbol's
 label to its .Lfunc_end: the instructions and the .amdhsa_kernel ... .end_amdhsa_kernel block (registers,
 LDS, scratch).  It renames the labels that depend on a function's index in its unit (.LBB<n>_<m>, .Lfunc_end<n>),
-drops comments and compares.  Exit status 0: same kernel names, no difference."""
+drops comments and compares.  For a kernel that differs it also says whether the counts per opcode and the
+descriptor's settings are equal: then the same instructions stand in another order.  Exit status 0: same kernel
+names, no difference."""
 import difflib
 import pathlib
 import re
@@ -41,6 +43,17 @@ def kernels(directory):
     return out
 
 
+def opcode_counts(body):
+    """{mnemonic: how often} over the instructions (no labels, no directives)"""
+    ops = [s.split()[0] for s in body if not s.startswith(".") and not s.endswith(":")]
+    return {op: ops.count(op) for op in set(ops)}
+
+
+def resources(body):
+    """the descriptor's settings: registers, LDS, scratch and what else .amdhsa_kernel ... .end_amdhsa_kernel holds"""
+    return [s for s in body if s.startswith(".amdhsa_") and not s.startswith(".amdhsa_kernel ")]
+
+
 def main():
     if len(sys.argv) != 3:
         sys.exit(__doc__)
@@ -52,7 +65,10 @@ def main():
     for k in only_new:
         print(f"only in {sys.argv[2]}: {k}")
     for k in differ:
-        print(f"differs: {k}")
+        same_ops = opcode_counts(old[k]) == opcode_counts(new[k])
+        same_res = resources(old[k]) == resources(new[k])
+        print(f"differs: {k} ({len(old[k])} -> {len(new[k])} lines; counts per opcode "
+              f"{'equal' if same_ops else 'DIFFER'}, descriptor resources {'equal' if same_res else 'DIFFER'})")
         for ln in list(difflib.unified_diff(old[k], new[k], "old", "new", lineterm="", n=1))[:40]:
             print("    " + ln)
     print(f"kernel_isa_diff: {len(old)} kernels old, {len(new)} new, {len(only_old)} only old, "
