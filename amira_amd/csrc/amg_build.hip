@@ -12,10 +12,10 @@
 //       amg_build_x_comp.hip    a filtered build's components and touched reads
 //     verified 64-bit fingerprints in 32-byte slots (2^29 tokens and more, a merged build whose tuple does not fit a slot,
 //     AMG_KEY_MODE=fp, AMG_COUNT_INLINE, a fitting tuple under the weak-fingerprint hook):
-//       amg_build_fp.hip bs_nodes_pass        local windows -> local node table (+ compaction list in s1 / s3)
-//                        bs_nodes_rank_local  single GPU: node ids from the local table
-//                        bs_edges_pass        local adjacencies -> local edge-class table (+ compaction list)
-//                        bs_pairs_from_local  single GPU: edge classes in first-seen order as arrays
+//       amg_build_fp.hip bs_nodes_pass        local windows -> local node table (+ its key list, ctx->fp_keys)
+//                        bs_nodes_rank_local  single GPU: node ids from the key list, sorted by first-seen (fp_list_sort)
+//                        bs_edges_pass        local adjacencies -> local edge-class table (+ its key list)
+//                        bs_pairs_from_local  single GPU: edge classes in first-seen order as arrays, from the key list
 //   coverage             amg_count.hip (count_ids), called by the node / edge-class stage of each scheme
 //   directed edges       bs_finish_from_pairs, here (the scan that emits them: amg_scan.hip)
 //   components, adjacency lists: on first use, amg_adjacency.hip (ensure_components / ensure_adjacency)

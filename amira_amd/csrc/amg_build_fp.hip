@@ -270,8 +270,8 @@ int bs_count_by_slot(amg_ctx* c, CountKind what, const int* slots, int* ids_scra
 }
 
 // ------------------------------------------------------------------ host stages
-// the tail of both table passes: (first_seen, slot) of the table's occupied slots into s1 / s3 (s2 / s4: where the sort
-// by first-seen puts them), their number into status word `counter`, and the status words to the host
+// the tail of both table passes: the key list of the table's occupied slots (c->fp_keys, with room for its sorted form),
+// their number into status word `counter`, and the status words to the host
 static int compact_table(amg_ctx* c, const DevBuf& tab, int64_t slots, int counter, unsigned long long* hs) {
   // worst case every slot is occupied; size scratch by min(slots, windows upper bound)
   const size_t max_keys = (size_t)((long long)slots < c->n_tokens ? slots : c->n_tokens) + 1;
@@ -282,7 +282,18 @@ static int compact_table(amg_ctx* c, const DevBuf& tab, int64_t slots, int count
   hipLaunchKernelGGL(k_compact_slots, dim3(nblk(slots, 2048)), dim3(256), 0, c->stream, tab.as<Slot>(),
                      (unsigned long long)slots, c->s1.as<unsigned long long>(), c->s3.as<unsigned int>(),
                      c->status.as<unsigned long long>() + counter);
-  return fetch_status(c, hs);
+  AMGCHK(fetch_status(c, hs));
+  c->fp_keys = FpKeyList{c->s1.as<unsigned long long>(), c->s3.as<unsigned int>(), c->s2.as<unsigned long long>(),
+                         c->s4.as<unsigned int>(), (long long)hs[counter]};
+  return AMG_OK;
+}
+
+int fp_list_sort(amg_ctx* c, const FpKeyList& list, int first_bits, unsigned long long* sorted_first_out) {
+  if (!list.first || list.first != c->s1.p || list.first_sorted != c->s2.p || list.slot != c->s3.p || list.slot_sorted != c->s4.p)
+    return amg_fail(AMG_E_STATE, "fp_list_sort: the key list is not the ctx's current one: something reserved scratch "
+                                 "between the table pass and its ranking");
+  return prim_sort_u64_u32(c, list.first, sorted_first_out ? sorted_first_out : list.first_sorted, list.slot, list.slot_sorted,
+                           (size_t)list.n, first_bits);
 }
 
 // returns AMG_OK, or AMG_E_OVERFLOW with *which = OV_NODE_TABLE (node table too small)
@@ -338,13 +349,11 @@ int bs_nodes_rank_local(amg_ctx* c) {
   c->n_nodes = c->n_local_nodes;
   const long long D = c->n_nodes;
   int first_bits = ilog2_ceil((uint64_t)(c->tok_total > 0 ? c->tok_total : 1) * 2 + 2) + 1;
-  AMGCHK(prim_sort_u64_u32(c, c->s1.as<unsigned long long>(), c->s2.as<unsigned long long>(),
-                           c->s3.as<unsigned int>(), c->s4.as<unsigned int>(), (size_t)D,
-                           first_bits));
+  const FpKeyList& keys = c->fp_keys;
+  AMGCHK(fp_list_sort(c, keys, first_bits));
   AMGCHK(bs_alloc_nodes(c, D));
   if (D > 0)
-    hipLaunchKernelGGL(k_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st,
-                       c->s2.as<unsigned long long>(), c->s4.as<unsigned int>(), D,
+    hipLaunchKernelGGL(k_assign_nodes, dim3(nblk(D, 256)), dim3(256), 0, st, keys.first_sorted, keys.slot_sorted, D,
                        c->node_tab.as<Slot>(), c->tokens.as<int>(), c->k, c->two_v,
                        (long long)c->tok_base, c->packed_nodes ? 1 : 0, c->node_tokens.as<int>(),
                        c->node_cov.as<unsigned int>(), c->node_first.as<long long>(),
@@ -402,19 +411,18 @@ int bs_pairs_from_local(amg_ctx* c) {
   c->n_pairs = P;
   AMGCHK(bs_alloc_pairs(c, P));
   int efirst_bits = ilog2_ceil((uint64_t)(c->tok_total > 0 ? c->tok_total : 1) * 8 + 8) + 1;
-  AMGCHK(prim_sort_u64_u32(c, c->s1.as<unsigned long long>(), c->pair_first.as<unsigned long long>(),
-                           c->s3.as<unsigned int>(), c->s4.as<unsigned int>(), (size_t)P,
-                           efirst_bits));
+  const FpKeyList& keys = c->fp_keys;
+  AMGCHK(fp_list_sort(c, keys, efirst_bits, c->pair_first.as<unsigned long long>()));
   if (P > 0)
     hipLaunchKernelGGL(k_gather_pairs, dim3(nblk(P, 256)), dim3(256), 0, st,
-                       c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot>(),
+                       keys.slot_sorted, P, c->edge_tab.as<Slot>(),
                        c->pair_key.as<unsigned long long>(), c->pair_cnt.as<unsigned int>());
   stage_end(c);
   if (!c->count_inline && P > 0) {
     // edge-class coverage: pair ids into the table, then count the per-adjacency slots
     stage_begin(c, "edge_count");
     hipLaunchKernelGGL(k_set_pair_ids, dim3(nblk(P, 256)), dim3(256), 0, st,
-                       c->s4.as<unsigned int>(), P, c->edge_tab.as<Slot>());
+                       keys.slot_sorted, P, c->edge_tab.as<Slot>());
     AMGCHK(count_ids(c, CountEdgeClasses, IdsPlain, c->tok_pair.as<int>(), c->n_tokens, P, c->pair_cnt.as<unsigned int>(),
                      c->edge_tab.as<Slot>()));
     stage_end(c);

@@ -477,7 +477,8 @@ static long long dense_tiles(long long head, long long n_tiles) {
 // The claim plan of one table pass (nodes or edge classes): where its claim ids come from and how many there can be.
 struct PassPlan {
   long long n_tiles;
-  bool rank_next;  // the caller ranks these claims before anybody else writes s0: the ranking's flag bytes are zeroed behind the read-back
+  bool rank_next;  // the caller ranks these claims next, with no other use of scratch in between: the ranking's flag bytes are zeroed
+                   // behind the read-back (rank_flags_zero_behind) and the proof goes to the ranking (RankFlagsZeroed)
   bool sharded;    // claims from the shard counters (then the ids in use have holes: space())
   unsigned int cap;          // claims per counter
   long long head;            // tiles of the head launch (0: none)

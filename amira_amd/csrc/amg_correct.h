@@ -250,17 +250,18 @@ struct CorrSwitches {
 };
 
 // The scratch plan: every array of a call that is carved out of a shared buffer, under the name the steps use.
-// (The per-read arrays must survive the scans, so each group has a buffer of its own.)
+// (The per-read arrays must survive the scans, so each group has a buffer of its own.)  The fields of one line share
+// one allocation, in the order written; the plan functions of amg_correct.hip own the buffers behind them.
 struct CorrScratch {
   size_t per_read = 0;  // n_reads + 2: the stride of the per-read arrays
-  unsigned char *cls = nullptr, *final_cls = nullptr;                        // s0
-  int *r_start = nullptr, *r_end = nullptr;                                  // s1
-  long long *nw_size = nullptr, *nw_off = nullptr;                           // s1, behind r_end at the next 16 bytes: per
-                                                                             // GAPPED read, global NW scratch bytes + prefix
-  unsigned int *bound = nullptr, *new_len = nullptr, *flag = nullptr;        // s2 (cleared as one range)
-  long long *tmp_off = nullptr, *new_idx = nullptr, *new_off = nullptr;      // s3
-  int* tmp_tok = nullptr;                                                    // s4: staged genes of the re-threaded reads
-  long long *plen = nullptr, *poffs = nullptr, *pos_new = nullptr;           // s5 (carry-over only): per gapped read new
+  unsigned char *cls = nullptr, *final_cls = nullptr;
+  int *r_start = nullptr, *r_end = nullptr;
+  long long *nw_size = nullptr, *nw_off = nullptr;                           // in r_end's allocation, behind it at the next 16
+                                                                             // bytes: per GAPPED read, global NW scratch bytes + prefix
+  unsigned int *bound = nullptr, *new_len = nullptr, *flag = nullptr;        // (cleared as one range)
+  long long *tmp_off = nullptr, *new_idx = nullptr, *new_off = nullptr;
+  int* tmp_tok = nullptr;                                                    // staged genes of the re-threaded reads
+  long long *plen = nullptr, *poffs = nullptr, *pos_new = nullptr;           // (carry-over only): per gapped read new
                                                                              // positions + prefix, per read its pool index
   // counters.  ST_MISC of the status words has two lives: the largest staging bound until the classify step's
   // fetch, the number of reads for the general carry-over kernel from k_nw_sizes on

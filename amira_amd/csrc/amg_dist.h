@@ -12,6 +12,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym
 
 #include "amg_device.h"
+#include "amg_read_walk.h"
 #include "amg_slot16.h"
 
 #define REC_BYTES 24    // {u64 merge key, u64 first-seen, u32 count, u32 pad}: what travels to the owners (both kinds)
@@ -71,6 +72,8 @@ struct WalkState {
   int64_t data_words = 0;                // 64-bit words a rank contributes to the data exchange
   DevBuf msg, msg_all;                   // this rank's header (+ the depth sums), the headers of all ranks: made at begin
   DevBuf send, recv;                     // the data exchange: this rank's part / the folded answer, the parts of all ranks
+  RwKeep kept;                           // what the local phase left for the fold (amg_read_walk.h): B's keep bytes and
+  RwComp comp;                           // kill marks, C's counts (the rank's part of the data exchange)
   bool have_result = false;
   std::vector<int64_t> result;           // amg_dist_walk_result
 };

@@ -319,8 +319,8 @@ static int edges_local_x(amg_ctx* c, DistState* d) {
   return r;
 }
 
-// fingerprint shards, after the table pass of a kind (0 nodes, 1 edge classes) left its compaction list in s1 (first) /
-// s3 (slot): local occurrence counts, the list in first-seen order, destinations
+// fingerprint shards, after the table pass of a kind (0 nodes, 1 edge classes) left its key list (c->fp_keys): local
+// occurrence counts, the list in first-seen order, destinations
 static int fp_records_local(amg_ctx* c, DistState* d, int kind) {
   hipStream_t st = c->stream;
   const int world = d->world;
@@ -331,19 +331,19 @@ static int fp_records_local(amg_ctx* c, DistState* d, int kind) {
   // Nodes: tok_node is free scratch until the edge pass writes it)
   const uint64_t first_top = kind ? (uint64_t)(c->tok_total > 0 ? c->tok_total : 1) * 8 + 8
                                   : (uint64_t)(c->n_tokens > 0 ? c->n_tokens : 1) * 2 + 2;
-  AMGCHK(prim_sort_u64_u32(c, c->s1.as<unsigned long long>(), c->s2.as<unsigned long long>(),
-                           c->s3.as<unsigned int>(), c->s4.as<unsigned int>(), (size_t)n, ilog2_ceil(first_top) + 1));
+  const FpKeyList& keys = c->fp_keys;
+  AMGCHK(fp_list_sort(c, keys, ilog2_ceil(first_top) + 1));
   AMGCHK(d->loc_cnt.ensure((size_t)(n + 2) * sizeof(unsigned int)));
   AMGCHK(bs_count_by_slot(c, kind ? CountEdgeClasses : CountNodes, kind ? c->tok_pair.as<int>() : c->tok_slot.as<int>(),
                           kind ? c->tok_pair.as<int>() : c->tok_node.as<int>(), c->n_tokens, tab,
-                          c->s4.as<unsigned int>(), n, d->loc_cnt.as<unsigned int>()));
+                          keys.slot_sorted, n, d->loc_cnt.as<unsigned int>()));
   Bucketing b;
   AMGCHK(bucketing(d, n, &b));
-  // keep the compaction list in first-seen order (s2 / s4: the sort's output): the later sorts use the generic scratch
+  // keep the sorted list in buffers of the merge's own: the later sorts use the generic scratch
   AMGCHK(d->loc_first.ensure((size_t)(n + 1) * sizeof(unsigned long long)));
   AMGCHK(d->loc_slot.ensure((size_t)(n + 1) * sizeof(unsigned int)));
-  HIPCHK(hipMemcpyAsync(d->loc_first.p, c->s2.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(d->loc_slot.p, c->s4.p, (size_t)n * sizeof(unsigned int), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(d->loc_first.p, keys.first_sorted, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(d->loc_slot.p, keys.slot_sorted, (size_t)n * sizeof(unsigned int), hipMemcpyDeviceToDevice, st));
   if (n > 0 && world > 1)
     hipLaunchKernelGGL(k_dist_dest, dim3(nblk(n, 256)), dim3(256), 0, st, d->loc_slot.as<unsigned int>(), n, tab,
                        (unsigned int)world, b.dest, b.idx);

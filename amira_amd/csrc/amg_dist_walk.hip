@@ -81,8 +81,8 @@ static int local_phase(amg_ctx* c, DistState* d, WalkState* w) {
       AMGCHK(w->send.ensure((size_t)words * sizeof(unsigned long long)));
       AMGCHK(w->recv.ensure((size_t)W * (size_t)words * sizeof(unsigned long long)));
       stage_begin(c, "amr_trim_local");
-      AMGCHK(rw_keep_local(c, w->gene_flags.data(), &w->flag_words));
-      hipLaunchKernelGGL(k_dw_pack_keep, dim3(nblk(words * 64, 256)), dim3(256), 0, c->stream, c->s4.as<unsigned char>(), D, words,
+      AMGCHK(rw_keep_local(c, w->gene_flags.data(), &w->flag_words, &w->kept));
+      hipLaunchKernelGGL(k_dw_pack_keep, dim3(nblk(words * 64, 256)), dim3(256), 0, c->stream, w->kept.keep, D, words,
                          w->send.as<unsigned long long>());
       stage_end(c);
       return AMG_OK;
@@ -94,7 +94,7 @@ static int local_phase(amg_ctx* c, DistState* d, WalkState* w) {
       if (nc == 0) return AMG_OK;
       AMGCHK(w->send.ensure(2 * (size_t)nc * sizeof(unsigned long long)));  // (the folded answer)
       AMGCHK(w->recv.ensure((size_t)W * 2 * (size_t)nc * sizeof(unsigned long long)));
-      return rw_comp_local(c, w->gene_flags.data(), w->min_genes[0], &w->flag_words);
+      return rw_comp_local(c, w->gene_flags.data(), w->min_genes[0], &w->flag_words, &w->comp);
     }
   }
 }
@@ -162,7 +162,7 @@ static int st_walk_judge(amg_ctx* c, DistState* d, WalkState* w, amg_xfer* x) {
   }
   w->state = W_FOLD;
   if (!wire) return 2;
-  const void* part = w->which == AMG_WALK_AMR_TRIM ? w->send.p : c->s4.p;
+  const void* part = w->which == AMG_WALK_AMR_TRIM ? w->send.p : w->comp.n_reads;
   dist_xfer_ag(d, x, part, w->recv.p, (int)sizeof(unsigned long long), w->data_words, true);
   return 1;
 }
@@ -174,18 +174,19 @@ static int st_walk_fold(amg_ctx* c, DistState* d, WalkState* w, amg_xfer*) {
   if (w->which == AMG_WALK_AMR_TRIM) {
     const long long D = c->n_nodes;
     const unsigned long long* all = wire ? w->recv.as<unsigned long long>() : w->send.as<unsigned long long>();
+    AMGCHK(kill_marks_check(c, w->kept.marks));  // (the caller's exchanges ran since the local phase reserved them)
     stage_begin(c, "amr_trim_fold");
     hipLaunchKernelGGL(k_dw_fold_kill, dim3(nblk(D, 256)), dim3(256), 0, c->stream, all, W, n, c->node_alive.as<unsigned char>(), D,
-                       c->s0.as<unsigned char>());
+                       w->kept.marks.bytes);
     c->have_corrected = false;
     int64_t n_removed = 0;
-    const int r = finish_kill(c, &n_removed, nullptr);
+    const int r = finish_kill(c, w->kept.marks, &n_removed, nullptr);
     stage_end(c);
     if (r != AMG_OK) return r;
     w->result.assign(1, n_removed);
     return 0;
   }
-  const unsigned long long* all = wire ? w->recv.as<unsigned long long>() : c->s4.as<unsigned long long>();
+  const unsigned long long* all = wire ? w->recv.as<unsigned long long>() : w->comp.n_reads;
   stage_begin(c, "amr_reads_fold");
   hipLaunchKernelGGL(k_dw_fold_sum, dim3(nblk(n, 256)), dim3(256), 0, c->stream, all, W, n, w->send.as<unsigned long long>());
   stage_end(c);
@@ -226,6 +227,8 @@ extern "C" int amg_dist_walk_begin(amg_ctx* c, int32_t which, const uint8_t* gen
   w->have_result = false;
   w->result.clear();
   w->data_words = 0;
+  w->kept = RwKeep();
+  w->comp = RwComp();
   w->hdr[DW_H_WHICH] = which;
   w->hdr[DW_H_STATUS] = 0;
   w->hdr[DW_H_K] = c->k;

@@ -330,14 +330,30 @@ __global__ void k_scatter_ids(const unsigned char* __restrict__ killed, const lo
   if (i < n && killed[i]) out[pos[i]] = (int)i;
 }
 
-// kill[] (s0) -> node_alive, removal side effects, ascending list of removed ids
-int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids) {
+int kill_marks_reserve(amg_ctx* c, ClearList* cl, KillMarks* marks) {
+  const long long D = c->n_nodes;
+  AMGCHK(c->s0.ensure((size_t)D + 8));
+  cl->add(c->s0.p, (size_t)D + 8);
+  *marks = KillMarks{c->s0.as<unsigned char>(), D};
+  return AMG_OK;
+}
+
+int kill_marks_check(const amg_ctx* c, const KillMarks& marks) {
+  if (!marks.bytes || marks.bytes != c->s0.p || marks.n != c->n_nodes)
+    return amg_fail(AMG_E_STATE, "the kill marks (%lld nodes) are not the ctx's current ones (%lld nodes): something else "
+                                 "ran on the ctx between their reservation and their use",
+                    marks.n, (long long)c->n_nodes);
+  return AMG_OK;
+}
+
+// marks -> node_alive, removal side effects, ascending list of removed ids
+int finish_kill(amg_ctx* c, const KillMarks& marks, int64_t* n_removed, int32_t* removed_ids) {
   hipStream_t st = c->stream;
   const long long D = c->n_nodes;
+  AMGCHK(kill_marks_check(c, marks));
   AMGCHK(c->s2.ensure((size_t)(D + 2) * sizeof(long long)));
-  // the scan applies what it counts: a marked live node dies, kill[] is left as "removed by this call"
-  AMGCHK(prim_exscan_apply_kill(c, c->s0.as<unsigned char>(), c->node_alive.as<unsigned char>(), c->s2.as<long long>(),
-                                (size_t)D));
+  // the scan applies what it counts: a marked live node dies, the marks are left as "removed by this call"
+  AMGCHK(prim_exscan_apply_kill(c, marks.bytes, c->node_alive.as<unsigned char>(), c->s2.as<long long>(), (size_t)D));
   long long total = 0;
   {
     FetchList l;
@@ -347,8 +363,8 @@ int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids) {
   if (n_removed) *n_removed = total;
   if (removed_ids && total > 0) {
     AMGCHK(c->s3.ensure((size_t)total * sizeof(int)));
-    hipLaunchKernelGGL(k_scatter_ids, dim3(nblk(D, 256)), dim3(256), 0, st, c->s0.as<unsigned char>(),
-                       c->s2.as<long long>(), D, c->s3.as<int>());
+    hipLaunchKernelGGL(k_scatter_ids, dim3(nblk(D, 256)), dim3(256), 0, st, marks.bytes, c->s2.as<long long>(), D,
+                       c->s3.as<int>());
     HIPCHK(hipMemcpyAsync(removed_ids, c->s3.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   if (total > 0) AMGCHK(apply_removals(c, 0));
@@ -381,13 +397,15 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
   stage_begin(c, "clip");
   // live nodes per component, and the mean node coverage's two integers (:868-871), in one pass
   unsigned long long* acc = c->status.as<unsigned long long>() + ST_COV_SUM;  // (the live adjacency below uses ST_COMPACT_*)
-  AMGCHK(c->s0.ensure((size_t)D + 8));
-  if (by_labels) AMGCHK(c->s4.ensure((size_t)(c->n_components + 2) * sizeof(unsigned int)));
+  KillMarks marks;
   {
     ClearList cl;
     cl.add(acc, 2 * sizeof(unsigned long long));
-    cl.add(c->s0.p, (size_t)D + 8);
-    if (by_labels) cl.add(c->s4.p, (size_t)(c->n_components + 2) * sizeof(unsigned int));
+    AMGCHK(kill_marks_reserve(c, &cl, &marks));
+    if (by_labels) {
+      AMGCHK(c->s4.ensure((size_t)(c->n_components + 2) * sizeof(unsigned int)));
+      cl.add(c->s4.p, (size_t)(c->n_components + 2) * sizeof(unsigned int));
+    }
     if (light) AMGCHK(row_summary_reserve(c, &cl));  // (its rows are zeroed with the rest)
     AMGCHK(clear_many(c, cl));
   }
@@ -409,13 +427,13 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
   const unsigned int* comp_live = by_labels ? c->s4.as<unsigned int>() : nullptr;
   if (light) {
     hipLaunchKernelGGL(k_clip_mark<RView>, dim3(nblk(D, 128)), dim3(128), 0, st, summary, D, (int)min_length, acc, comp_live,
-                       d_protect, c->s0.as<unsigned char>());
+                       d_protect, marks.bytes);
   } else {
     AMGCHK(ensure_live_adj(c));
     hipLaunchKernelGGL(k_clip_mark<GView>, dim3(nblk(D, 128)), dim3(128), 0, st, make_view(c), D, (int)min_length, acc,
-                       comp_live, d_protect, c->s0.as<unsigned char>());
+                       comp_live, d_protect, marks.bytes);
   }
-  int r = finish_kill(c, n_removed, removed_ids);
+  int r = finish_kill(c, marks, n_removed, removed_ids);
   stage_end(c);
   c->have_corrected = false;
   return r;
@@ -436,11 +454,11 @@ extern "C" int amg_remove_low_coverage_components(amg_ctx* c, uint32_t min_cov) 
   if (D == 0) return AMG_OK;
   AMGCHK(ensure_components(c));
   size_t nc = (size_t)(c->n_components + 2);
-  AMGCHK(c->s0.ensure((size_t)D + 8));
-  AMGCHK(c->s4.ensure(2 * nc * sizeof(unsigned int)));
+  KillMarks marks;
   {
     ClearList cl;
-    cl.add(c->s0.p, (size_t)D + 8);
+    AMGCHK(kill_marks_reserve(c, &cl, &marks));
+    AMGCHK(c->s4.ensure(2 * nc * sizeof(unsigned int)));
     cl.add(c->s4.p, 2 * nc * sizeof(unsigned int));
     AMGCHK(clear_many(c, cl));
   }
@@ -450,7 +468,7 @@ extern "C" int amg_remove_low_coverage_components(amg_ctx* c, uint32_t min_cov) 
                      c->node_alive.as<unsigned char>(), c->node_cov.as<unsigned int>(), D, min_cov, live, high,
                      (unsigned long long*)nullptr);
   hipLaunchKernelGGL(k_kill_low_components, dim3(nblk(D, 256)), dim3(256), 0, st, c->node_comp.as<int>(),
-                     c->node_alive.as<unsigned char>(), high, D, c->s0.as<unsigned char>());
+                     c->node_alive.as<unsigned char>(), high, D, marks.bytes);
   c->have_corrected = false;
-  return finish_kill(c, nullptr, nullptr);
+  return finish_kill(c, marks, nullptr, nullptr);
 }

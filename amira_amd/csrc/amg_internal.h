@@ -160,6 +160,17 @@ enum class LiveLists {
   BehindNodes,  // the lists of the graph before some NODES died (no edge died with both ends alive): k_lr_patch brings them up to date
 };
 
+// The key list of a table pass on the fingerprint path (amg_build_fp.hip): (first_seen, slot) of the table's n occupied
+// slots in any order, and where fp_list_sort puts them in first-seen order.  Device pointers into the ctx's scratch: the
+// list holds from the pass that made it (bs_nodes_pass, bs_edges_pass) to the one consumer that follows it.
+struct FpKeyList {
+  const unsigned long long* first = nullptr;
+  const unsigned int* slot = nullptr;
+  unsigned long long* first_sorted = nullptr;
+  unsigned int* slot_sorted = nullptr;
+  long long n = 0;
+};
+
 struct amg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -194,6 +205,7 @@ struct amg_ctx {
   int64_t hint_bound = 0;    // amg_set_reads_from_corrected: the source's bound for THESE reads, applied by a build at hint_bound_k
   int hint_bound_k = 0;
   int64_t n_local_nodes = 0, n_local_pairs = 0;  // before a multi-GPU merge
+  FpKeyList fp_keys;      // fingerprint path: the key list of the last table pass (n = n_local_nodes or n_local_pairs)
   int64_t tok_base = 0;   // global index of this shard's first token (0 on a single GPU)
   int64_t tok_total = 0;  // tokens over all shards
 
@@ -227,7 +239,7 @@ struct amg_ctx {
   // live adjacency (only alive edges, targets inline) — made on first use after removals (amg_live_rows.hip)
   DevBuf ladj;      // int2[n_live_edges]  {target node, target direction}
   DevBuf ladj_rows; // int4[2 n_nodes]  {offset, live count, first target, first direction}
-  DevBuf ladj_pos, ladj_keys;  // scratch of the live-adjacency build (callers hold s0..s5)
+  DevBuf ladj_pos, ladj_keys;  // scratch of the live-adjacency build; it must never use the general scratch arrays, which its callers hold across it
   DevBuf hub_bits;             // bitmaps over the edge ids for adjacency rows beyond HUGE_ROW (huge_row_in_order, amg_rows.h)
   LiveLists live_lists = LiveLists::Absent;
   bool comp_valid = false, adj_valid = false;  // component ids / full edge lists of the built graph are made on demand
@@ -294,7 +306,9 @@ struct amg_ctx {
   DevBuf scan_state;   // amg_scan.hip: ticket counter + one status word per tile
   unsigned long long scan_tickets = 0;  // tiles all scans so far have used
   unsigned int scan_epoch = 0;
-  DevBuf s0, s1, s2, s3, s4, s5;  // general scratch arrays
+  // general scratch arrays, each private to the function that ensures it: what outlives that function travels as a
+  // named value (KillMarks, FpKeyList, RankFlagsZeroed, the results of amg_read_walk.h), never as a buffer number
+  DevBuf s0, s1, s2, s3, s4, s5;
   DevBuf nw_big;       // global scratch of the general position carry-over kernel (long reads)
   DevBuf gap_rec;      // per gapped read: the record k_corr_gapped_fast starts from
   // path memo of the re-threading (amg_gap_memo.hip: k_gap_queries / k_gap_dfs)
@@ -427,9 +441,21 @@ GView make_view(amg_ctx* c);
 void live_lists_after_node_deaths(amg_ctx* c);  // nodes died, and every edge that died has a dead end
 void live_lists_after_edge_deaths(amg_ctx* c);  // an edge died with both its ends alive
 void live_lists_after_build(amg_ctx* c);        // a new graph
-// amg_filter.hip: the nodes marked in s0 (a byte each, D + 8 bytes zeroed before the marking) die, with everything a
-// removal brings: edges, masked windows, read_fix, live lists.  Uses s2 (and s3 for the ids); waits for the count.
-int finish_kill(amg_ctx* c, int64_t* n_removed, int32_t* removed_ids);
+// Kill marks (amg_filter.hip): a byte per node, non-zero = the node is to die.  kill_marks_reserve hands them out and puts
+// their n + 8 bytes on the caller's ClearList, so they are zero once that list has been cleared; the caller's kernels mark
+// through the value; finish_kill uses it up.  Between the two nothing else may reserve marks on the ctx.
+struct KillMarks {
+  unsigned char* bytes = nullptr;
+  long long n = 0;  // nodes (c->n_nodes when they were reserved)
+};
+int kill_marks_reserve(amg_ctx* c, ClearList* cl, KillMarks* marks);
+// AMG_OK, or AMG_E_STATE when the marks are not the ctx's current ones for its n_nodes nodes.  finish_kill asks; so
+// does a caller that marks in a later call than the one that reserved (the fold of a walk across ranks)
+int kill_marks_check(const amg_ctx* c, const KillMarks& marks);
+// The marked nodes die, with everything a removal brings: edges, masked windows, read_fix, live lists.  *n_removed = how
+// many were alive, removed_ids (or null) = their ids, ascending; the count has been waited for.  Marks that are not the
+// ctx's current ones for its n_nodes nodes are refused (AMG_E_STATE) before anything is read or changed.
+int finish_kill(amg_ctx* c, const KillMarks& marks, int64_t* n_removed, int32_t* removed_ids);
 void bubbles_release(amg_ctx* c);  // amg_bubbles.hip
 void sketch_release(amg_ctx* c);   // amg_sketch.hip
 void pop_release(amg_ctx* c);  // amg_pop.hip
@@ -455,6 +481,9 @@ int bs_nodes_pass(amg_ctx* c, int k, Overflow* which);
 int bs_nodes_rank_local(amg_ctx* c);
 int bs_edges_pass(amg_ctx* c, Overflow* which);
 int bs_pairs_from_local(amg_ctx* c);
+// list in first-seen order (keys of first_bits bits): slots into slot_sorted, first-seen values into sorted_first_out
+// or, without one, first_sorted.  A list that is not the ctx's current one is refused (AMG_E_STATE).
+int fp_list_sort(amg_ctx* c, const FpKeyList& list, int first_bits, unsigned long long* sorted_first_out = nullptr);
 // the views of a built graph that are made on first use (amg_adjacency.hip)
 int ensure_components(amg_ctx* c);
 int ensure_adjacency(amg_ctx* c);

@@ -393,17 +393,21 @@ static void rw_launch(amg_ctx* c, const RwArgs& g, const Use& use) {
                      g, use);
 }
 
-// gene_flags[V] (host bytes) as a bitmap in s5; `words` holds the host copy until the stream has taken it
-static int rw_upload_flags(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned int>* words) {
+// gene_flags[V] (host bytes) as a bitmap on the device; `words` holds the host copy until the stream has taken it
+struct RwFlagBits {
+  const unsigned int* bits = nullptr;
+  int words = 0;
+};
+static int rw_upload_flags(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned int>* words, RwFlagBits* out) {
   const int V = c->two_v / 2;
   words->assign((size_t)(V + 31) / 32, 0u);
   for (int r = 0; r < V; ++r)
     if (gene_flags[r]) (*words)[(size_t)r >> 5] |= 1u << (r & 31);
   AMGCHK(c->s5.ensure(words->size() * sizeof(unsigned int) + 64));
   HIPCHK(hipMemcpyAsync(c->s5.p, words->data(), words->size() * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+  *out = RwFlagBits{c->s5.as<unsigned int>(), (int)words->size()};
   return AMG_OK;
 }
-
 
 // ---- the local phases: the walks over the reads THIS ctx holds.  The single-GPU entry points below are a local phase
 // and a read-back; the walks across ranks (amg_dist_walk.hip) put an exchange and a fold between the two.
@@ -426,22 +430,21 @@ int rw_depth_local(amg_ctx* c, const int32_t* min_genes, int32_t n, unsigned lon
   return AMG_OK;
 }
 
-int rw_keep_local(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned int>* words) {
+int rw_keep_local(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned int>* words, RwKeep* out) {
   const long long D = c->n_nodes;
-  AMGCHK(rw_upload_flags(c, gene_flags, words));
-  AMGCHK(c->s0.ensure((size_t)D + 8));
+  RwFlagBits flags;
+  AMGCHK(rw_upload_flags(c, gene_flags, words, &flags));
+  ClearList cl;
+  AMGCHK(kill_marks_reserve(c, &cl, &out->marks));
   AMGCHK(c->s1.ensure((size_t)c->n_reads + 8));
   AMGCHK(c->s4.ensure((size_t)D + 8));
-  {
-    ClearList cl;
-    cl.add(c->s0.p, (size_t)D + 8);
-    cl.add(c->s4.p, (size_t)D + 8);
-    AMGCHK(clear_many(c, cl));
-  }
+  cl.add(c->s4.p, (size_t)D + 8);
+  AMGCHK(clear_many(c, cl));
+  out->keep = c->s4.as<unsigned char>();
   if (c->n_reads > 0) {
     HitUse hit;
     hit.hit = c->s1.as<unsigned char>();
-    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words->size()), hit);
+    rw_launch(c, rw_args(c, flags.bits, flags.words), hit);
     KeepUse keep;
     keep.hit = c->s1.as<unsigned char>();
     keep.keep = c->s4.as<unsigned char>();
@@ -450,10 +453,11 @@ int rw_keep_local(amg_ctx* c, const uint8_t* gene_flags, std::vector<unsigned in
   return AMG_OK;
 }
 
-int rw_comp_local(amg_ctx* c, const uint8_t* gene_flags, int32_t min_genes, std::vector<unsigned int>* words) {
+int rw_comp_local(amg_ctx* c, const uint8_t* gene_flags, int32_t min_genes, std::vector<unsigned int>* words, RwComp* out) {
   const long long nc = c->n_components;
   stage_begin(c, "amr_reads");
-  AMGCHK(rw_upload_flags(c, gene_flags, words));
+  RwFlagBits flags;
+  AMGCHK(rw_upload_flags(c, gene_flags, words, &flags));
   const size_t out_bytes = 2 * (size_t)nc * sizeof(unsigned long long);
   AMGCHK(c->s4.ensure(out_bytes));
   {
@@ -461,13 +465,15 @@ int rw_comp_local(amg_ctx* c, const uint8_t* gene_flags, int32_t min_genes, std:
     cl.add(c->s4.p, out_bytes);
     AMGCHK(clear_many(c, cl));
   }
+  unsigned long long* counts = c->s4.as<unsigned long long>();
+  *out = RwComp{counts, counts + nc, nc};
   if (c->n_reads > 0) {
     CompUse use;
-    use.n_reads = c->s4.as<unsigned long long>();
-    use.n_long = use.n_reads + nc;
+    use.n_reads = counts;
+    use.n_long = counts + nc;
     use.n_comp = (int)nc;
     use.min_genes = min_genes;
-    rw_launch(c, rw_args(c, c->s5.as<unsigned int>(), (int)words->size()), use);
+    rw_launch(c, rw_args(c, flags.bits, flags.words), use);
   }
   stage_end(c);
   return AMG_OK;
@@ -500,11 +506,12 @@ extern "C" int amg_remove_non_amr_nodes(amg_ctx* c, const uint8_t* gene_flags, i
   stages_reset(c);
   stage_begin(c, "amr_trim");
   std::vector<unsigned int> words;
-  AMGCHK(rw_keep_local(c, gene_flags, &words));
+  RwKeep kept;
+  AMGCHK(rw_keep_local(c, gene_flags, &words, &kept));
   hipLaunchKernelGGL(k_rw_kill_unkept, dim3(nblk(D, 256)), dim3(256), 0, c->stream, c->node_alive.as<unsigned char>(),
-                     c->s4.as<unsigned char>(), D, c->s0.as<unsigned char>());
+                     kept.keep, D, kept.marks.bytes);
   c->have_corrected = false;
-  const int r = finish_kill(c, n_removed, nullptr);  // (waits for the stream: `words` has been taken)
+  const int r = finish_kill(c, kept.marks, n_removed, nullptr);  // (waits for the stream: `words` has been taken)
   stage_end(c);
   return r;
 }
@@ -521,10 +528,10 @@ extern "C" int amg_component_amr_reads(amg_ctx* c, const uint8_t* gene_flags, in
   if (cap < nc) return amg_fail(AMG_E_ARG, "room for %lld components, the graph has %lld", (long long)cap, nc);
   if (nc == 0) return AMG_OK;
   std::vector<unsigned int> words;
-  AMGCHK(rw_comp_local(c, gene_flags, min_genes, &words));
-  HIPCHK(hipMemcpyAsync(n_reads, c->s4.p, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(n_long, c->s4.as<unsigned long long>() + nc, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost,
-                        c->stream));
+  RwComp counts;
+  AMGCHK(rw_comp_local(c, gene_flags, min_genes, &words, &counts));
+  HIPCHK(hipMemcpyAsync(n_reads, counts.n_reads, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(n_long, counts.n_long, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return AMG_OK;
 }
