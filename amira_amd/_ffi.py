@@ -40,6 +40,8 @@ class Xfer(C.Structure):
 
 XFER_ALL_TO_ALL, XFER_ALL_GATHER = 1, 2
 WALK_DEPTH, WALK_AMR_TRIM, WALK_COMPONENT_READS = 1, 2, 3   # include/amg.h AMG_WALK_*
+SELECT_VALID, SELECT_JUNK = 0, 1                            # include/amg.h AMG_SELECT_*
+SEL_REJECTED, SEL_KEPT, SEL_UNLISTED = 0, 1, 2              # include/amg.h AMG_SEL_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -96,6 +98,7 @@ def _load():
         "amg_get_corrected_positions32": (C.c_int, [P, P, P]),
         "amg_adopt_corrected": (C.c_int, [P]),
         "amg_set_reads_from_corrected": (C.c_int, [P, P]),
+        "amg_select_reads": (C.c_int, [P, I32, I32, P, I64, P, C.POINTER(I64), C.POINTER(I64)]),
         "amg_match_patterns": (C.c_int, [P, C.c_int, P, P, I64, P, P, P]),
         "amg_minhash": (C.c_int, [P, P, P, P, I64, I32, C.c_uint64, P, P, I64, C.POINTER(I64)]),
         "amg_junction_paths": (C.c_int, [P, I32, C.POINTER(I64)]),

@@ -10,6 +10,8 @@ libamg.so (HIP, gfx950) through amira_amd.engine:
     remove_short_linear_paths         amg_remove_short_linear_paths
     remove_low_coverage_components    amg_remove_low_coverage_components
     correct_reads                     amg_correct_reads (+ amg_get_corrected)
+    remove_junk_reads,
+    get_valid_reads_only              amg_select_reads
 
 The device keeps the graph as integer arrays (DESIGN.md "Data layout").  The reference's
 object API (dicts keyed by 256-bit sha256 hashes, Node / Edge objects, per-read lists) is a
@@ -776,19 +778,29 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
         return new_reads, new_positions, rejected_reads, rejected_read_positions
 
     def _remove_junk_reads_arrays(self, error_rate):
-        """remove_junk_reads from the device's per-window node ids: masked windows per read by one segmented sum, the
-        reference's round() (half to even, in double arithmetic) by numpy's rint of the same product"""
-        tok_node, _ = self._engine.read_nodes()
-        offs, k = self._read_off, self._kmerSize
-        n_win = np.maximum(np.diff(offs) - k + 1, 0) if len(offs) > 1 else np.zeros(0, np.int64)
-        rows = np.flatnonzero(n_win > 0)            # the reads get_readNodes() lists, in read order
-        masked_tok = (tok_node == -2).astype(np.int64)
-        csum = np.concatenate([[0], np.cumsum(masked_tok)])
-        masked = csum[offs[rows] + n_win[rows]] - csum[offs[rows]]
-        allowed = np.rint(n_win[rows].astype(np.float64) * (1 - error_rate))
-        ok = masked <= allowed
-        keep_rows, drop_rows = rows[ok], rows[~ok]
-        if self._tokenized_io(self._genePositions is not None) and self._genePositions is not None:
+        """remove_junk_reads on the device (amg_select_reads, AMG_SELECT_JUNK): the masked windows of every read are
+        counted where the per-window node ids live, and the table they are held against is the reference's own
+        expression, allowed[w] = round(w * (1 - error_rate)) by the interpreter's round for every window count a read
+        can have.  Array-backed inputs: the rejected reads (the inverted selection) are fetched at once, the kept ones
+        stay on the device as a corrected set in which nothing changed (amira_amd.io.DeviceCorrected) for the next
+        GeneMerGraph to take over.  Dict inputs: dicts, the rows taken from the verdicts."""
+        offs, k = self._read_off, self._kmer_for_device()
+        longest = max(int(np.diff(offs).max()) - k + 1, 0) if len(offs) > 1 else 0
+        allowed = [round(w * (1 - error_rate)) for w in range(longest + 1)]
+        eng = self._engine
+        self._settle_leases()   # the selection overwrites the engine's corrected set
+        arrays = self._tokenized_io(self._genePositions is not None) and self._genePositions is not None
+        if arrays and not self._reads.edited() and self._genePositions.as_made():
+            if self._positions_pending:   # a graph of build_many: its engine has not seen the positions yet
+                self._upload_positions()
+            _, n_reads, n_tokens = eng.select_reads(_ffi.SELECT_JUNK, True, allowed, want_verdict=False)
+            rejected = self._selection_on_host(n_reads, n_tokens)
+            _, n_reads, n_tokens = eng.select_reads(_ffi.SELECT_JUNK, False, allowed, want_verdict=False)
+            kept = self._corrected_as_arrays(eng.corrected_index(n_reads), n_reads, n_tokens, True)
+            return kept + rejected
+        verdict, _, _ = eng.select_reads(_ffi.SELECT_JUNK, False, allowed)
+        keep_rows, drop_rows = np.flatnonzero(verdict == _ffi.SEL_KEPT), np.flatnonzero(verdict == _ffi.SEL_REJECTED)
+        if arrays:   # (mappings edited since the build: what they hold now, gathered on the host)
             return (self._reads.subset(keep_rows), self._genePositions.subset(keep_rows),
                     self._reads.subset(drop_rows), self._genePositions.subset(drop_rows))
         ids, reads, pos = self._read_ids, self._reads, self._genePositions
@@ -797,7 +809,29 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
         return ({r: reads[r] for r in keep}, {r: pos[r] for r in keep},
                 {r: reads[r] for r in drop}, {r: pos[r] for r in drop})
 
+    def _selection_on_host(self, n_reads, n_tokens):
+        """the engine's selected set as (reads, positions) over host arrays, fetched now, positions as int32 when they fit"""
+        src = getattr(self._reads, "source_rows", None)
+        source_ids = self._reads.read_ids if src is None else self._reads.source_ids
+        if n_reads == 0:
+            offs = np.zeros(1, np.int64)
+            none = np.zeros(0, np.int32)
+            return (TokenizedReads(self._vocab, none, offs, [], source_rows=np.zeros(0, np.int64), source_ids=source_ids),
+                    TokenizedPositions([], offs, none, none))
+        out = self._engine.corrected(n_reads, n_tokens, True, pos32=True)
+        orig, offs = out["orig_read"], out["read_offsets"]
+        ids = self._read_ids if len(orig) == len(self._read_ids) else self._names_of_rows(orig)
+        reads = TokenizedReads(self._vocab, out["tokens"], offs, ids,
+                               source_rows=orig.astype(np.int64) if src is None else src[orig], source_ids=source_ids)
+        return reads, TokenizedPositions(ids, offs, out["gene_start"], out["gene_end"])
+
     def get_valid_reads_only(self):
+        """the reads that are not marked for correction (:1422-1427).  Array-backed reads: selected on the device
+        (amg_select_reads, AMG_SELECT_VALID) and handed back as a TokenizedReads over a DeviceCorrected"""
+        if not self._host_edits and isinstance(self._reads, TokenizedReads) and not self._reads.edited():
+            self._settle_leases()   # the selection overwrites the engine's corrected set
+            _, n_reads, n_tokens = self._engine.select_reads(_ffi.SELECT_VALID, want_verdict=False)
+            reads, _ = self._corrected_as_arrays(self._engine.corrected_index(n_reads), n_reads, n_tokens, False)
+            return reads
         fix = self.get_reads_to_correct()
         return {r: g for r, g in self._reads.items() if r not in fix}
-

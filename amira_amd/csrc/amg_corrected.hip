@@ -36,7 +36,7 @@ static int to_host(amg_ctx* c, void* dst, const DevBuf& src, size_t bytes) {
 extern "C" int amg_get_corrected(amg_ctx* c, int32_t* tokens, int64_t* read_offsets, int32_t* orig_read,
                                  uint8_t* changed, int64_t* gene_start, int64_t* gene_end) {
   if (!c) return amg_fail(AMG_E_ARG, "null ctx");
-  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads first");
+  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads or amg_select_reads first");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   AMGCHK(to_host(c, tokens, c->c_tokens_buf, (size_t)c->c_tokens * sizeof(int32_t)));
@@ -158,7 +158,7 @@ extern "C" int amg_get_corrected32(amg_ctx* c, int32_t* tokens, int64_t* read_of
                                    uint8_t* changed, int64_t* pos_src, int32_t* new_start, int32_t* new_end,
                                    int64_t* n_new) {
   if (!c) return amg_fail(AMG_E_ARG, "null ctx");
-  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads first");
+  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads or amg_select_reads first");
   if (!pos_src || !n_new) return amg_fail(AMG_E_ARG, "amg_get_corrected32: pos_src and n_new are required");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void k_gather_positions32(CorrArgs a, const lo
 
 extern "C" int amg_get_corrected_positions32(amg_ctx* c, int32_t* gene_start, int32_t* gene_end) {
   if (!c || !gene_start || !gene_end) return amg_fail(AMG_E_ARG, "null argument");
-  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads first");
+  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads or amg_select_reads first");
   if (!c->have_pos) return amg_fail(AMG_E_STATE, "no gene positions were set");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -258,7 +258,7 @@ extern "C" int amg_get_corrected_positions32(amg_ctx* c, int32_t* gene_start, in
 
 extern "C" int amg_adopt_corrected(amg_ctx* c) {
   if (!c) return amg_fail(AMG_E_ARG, "null ctx");
-  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads first");
+  if (!c->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads or amg_select_reads first");
   // borrowed genes / offsets / lengths go back to their owner: the corrected set lives in our own
   // allocations.  The position arrays stay where they are (borrowed or not): corrected reads point
   // into them and into the pool of produced positions.
@@ -323,7 +323,7 @@ extern "C" int amg_adopt_corrected(amg_ctx* c) {
 // Positions are gathered into flat arrays of dst's own (pool 0, identity offsets); src keeps its corrected set.
 extern "C" int amg_set_reads_from_corrected(amg_ctx* dst, amg_ctx* src) {
   if (!dst || !src) return amg_fail(AMG_E_ARG, "null ctx");
-  if (!src->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads on the source ctx first");
+  if (!src->have_corrected) return amg_fail(AMG_E_STATE, "amg_correct_reads or amg_select_reads on the source ctx first");
   if (dst == src) return amg_adopt_corrected(src);
   if (dst->device != src->device) return amg_fail(AMG_E_ARG, "amg_set_reads_from_corrected: one device");
   HIPCHK(hipSetDevice(dst->device));

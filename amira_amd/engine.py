@@ -280,6 +280,17 @@ class Engine:
         check(_ffi.lib.amg_correct_reads(self._h, C.byref(nr), C.byref(nt)))
         return nr.value, nt.value
 
+    def select_reads(self, mode, invert=False, allowed=None, want_verdict=True):
+        """a selection of whole reads left on the device as the corrected set (amg_select_reads; mode: _ffi.SELECT_*,
+        allowed: the JUNK table, allowed[w] for a read of w windows).  Returns (verdict, n_reads, n_tokens): a
+        _ffi.SEL_* byte per read of the current set (None with want_verdict=False) and the sizes of the selected set"""
+        table = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.int64)
+        verdict = np.empty(self.sizes()[0], np.uint8) if want_verdict else None
+        nr, nt = C.c_int64(0), C.c_int64(0)
+        check(_ffi.lib.amg_select_reads(self._h, int(mode), 1 if invert else 0, ptr(table),
+                                        0 if table is None else len(table), ptr(verdict), C.byref(nr), C.byref(nt)))
+        return verdict, nr.value, nt.value
+
     ROUTES = ("gapped", "by_lean", "by_fast", "by_general", "on_not_tried", "on_windows", "on_runs", "on_memo_unfit",
               "on_records", "on_combos", "on_cand", "lean_no_slots", "lean_answers", "lean_long", "lean_other",
               "no_memo_slots", "memo_questions", "memo_spilled", "memo_unfit", "pool_retries", "keep_orig",

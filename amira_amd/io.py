@@ -14,8 +14,10 @@ from .tokens import Vocabulary
 
 
 class DeviceCorrected:
-    """What one GeneMerGraph.correct_reads produced, still on the device: the corrected genes and their positions
-    (240 MB + 960 MB for a million 60-gene reads).  The array-backed mappings correct_reads hands back point here;
+    """The corrected set of an engine, still on the device: what one GeneMerGraph.correct_reads produced — the
+    corrected genes and their positions (240 MB + 960 MB for a million 60-gene reads) — or what a selection of whole
+    reads left there (amg_select_reads: the reads remove_junk_reads keeps, the reads of get_valid_reads_only; a
+    corrected set in which nothing changed).  The array-backed mappings those methods hand back point here;
     the arrays cross PCIe only if somebody looks at them on the host — a GeneMerGraph built from those mappings takes
     them over device to device (amg_set_reads_from_corrected).  Holds the ENGINE whose buffers these are — not the
     graph, whose own gene positions point back here (a cycle would leave graph and engine to the cyclic collector) —

@@ -261,6 +261,26 @@ int amg_adopt_corrected(amg_ctx* ctx);
  * set; dst == src is amg_adopt_corrected.  Same device; synchronous. */
 int amg_set_reads_from_corrected(amg_ctx* dst, amg_ctx* src);
 
+/* ---- selections of whole reads, left on the device as a corrected set in which nothing changed
+ *      (amira_amd/csrc/amg_select.hip) ------------------------------------------------------------------------
+ * AMG_SELECT_VALID  get_valid_reads_only (construct_graph.py:1422-1427): read r is KEPT when it is not marked for
+ *                   correction (the flag of amg_get_reads_to_correct), else REJECTED.  Every read is listed, reads
+ *                   with fewer than k genes or none included.
+ * AMG_SELECT_JUNK   remove_junk_reads (construct_graph.py:1398-1420): w = max(genes - k + 1, 0) windows; w == 0 is
+ *                   UNLISTED (no entry in _readNodes: the read belongs to neither set); else m = the read's windows
+ *                   whose node was removed, KEPT when m <= allowed[w].  allowed: n_allowed HOST values, the
+ *                   reference's round(w * (1 - error_rate)) made by the caller; a read with w >= n_allowed is
+ *                   AMG_E_ARG, and no corrected set is left.
+ * verdict (n_reads host bytes, or NULL) does not depend on invert.  The selected set — the reads whose verdict is
+ * KEPT (invert == 0) or REJECTED (invert != 0), in read order, a read without genes included — becomes the ctx's
+ * corrected set exactly as an amg_correct_reads that changed no read would leave it: amg_get_corrected* (changed all
+ * 0), amg_adopt_corrected and amg_set_reads_from_corrected work on it; gene positions are not moved.  The graph is not
+ * changed.  Allowed on a graph made by amg_dist_merge*: a rank selects among its own reads, nothing is exchanged. */
+enum { AMG_SELECT_VALID = 0, AMG_SELECT_JUNK = 1 };
+enum { AMG_SEL_REJECTED = 0, AMG_SEL_KEPT = 1, AMG_SEL_UNLISTED = 2 };
+int amg_select_reads(amg_ctx* ctx, int32_t mode, int32_t invert, const int64_t* allowed, int64_t n_allowed,
+                     uint8_t* verdict, int64_t* n_out_reads, int64_t* n_out_tokens);
+
 /* ---- read-path clustering support: batched exact sub-list search
  *      (is_sublist / find_sublist_indices, construct_graph.py:1957-1966,2117-2123;
  *      Tree.find_all call sites path_finding_utils.py:244,290) ------------------------ */
