@@ -244,17 +244,7 @@ extern "C" int amg_set_reads(amg_ctx* c, const int32_t* tokens, const int64_t* r
   AMGCHK(copy_in(c, c->tokens, tokens, (size_t)n_tokens * sizeof(int32_t), on_device));
   AMGCHK(copy_in(c, c->read_off, read_offsets, (size_t)(n_reads + 1) * sizeof(int64_t), on_device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->n_reads = n_reads;
-  c->n_tokens = n_tokens;
-  c->two_v = two_v;
-  c->have_pos = c->have_read_len = false;
-  c->built = false;
-  c->derive_ready = c->dist_candidate = false;
-  c->hint_bound = 0;
-  c->have_corrected = false;
-  c->match_valid = false;
-  c->node_hint = 0;
-  c->cnt_hint_reset = true;  // what the counting sweeps learned belongs to the previous read set
+  ctx_reads_replaced(c, n_reads, n_tokens, two_v);
   return AMG_OK;
 }
 
@@ -266,16 +256,10 @@ extern "C" int amg_set_positions(amg_ctx* c, const int64_t* gene_start, const in
   HIPCHK(hipSetDevice(c->device));
   AMGCHK(copy_in(c, c->gene_start, gene_start, (size_t)c->n_tokens * sizeof(int64_t), on_device));
   AMGCHK(copy_in(c, c->gene_end, gene_end, (size_t)c->n_tokens * sizeof(int64_t), on_device));
-  c->have_pos = true;
-  c->pos_identity = true;
-  c->pos0_own = false;
-  c->pos_n0 = c->n_tokens;
-  c->pos1_used = c->c_pos1_used = 0;
-  c->have_corrected = false;
-  c->have_read_len = false;
+  ctx_positions_replaced(c, c->n_tokens, false);
   if (read_len) {
     AMGCHK(copy_in(c, c->read_len, read_len, (size_t)c->n_reads * sizeof(int64_t), on_device));
-    c->have_read_len = true;
+    ctx_read_lengths_set(c);
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   return AMG_OK;
@@ -286,7 +270,7 @@ extern "C" int amg_set_read_lengths(amg_ctx* c, const int64_t* read_len, int on_
   if (c->two_v <= 0) return amg_fail(AMG_E_STATE, "amg_set_reads first");
   HIPCHK(hipSetDevice(c->device));
   AMGCHK(copy_in(c, c->read_len, read_len, (size_t)c->n_reads * sizeof(int64_t), on_device));
-  c->have_read_len = true;
+  ctx_read_lengths_set(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   return AMG_OK;
 }

@@ -111,13 +111,7 @@ int bs_finish_from_pairs(amg_ctx* c) {
   }
   c->n_edges = total;
   stage_end(c);
-  live_lists_after_build(c);
-  c->pristine = !c->comp_from_claims;  // (a filtered build's labels are those of the graph BEFORE its filter)
-  c->edge_own_deaths = false;
-  c->comp_valid = false;
-  c->adj_valid = false;
-  c->n_components = 0;
-  return AMG_OK;
+  return AMG_OK;  // (the caller says that a graph is in place: ctx_graph_in_place)
 }
 
 extern "C" int amg_finalize(amg_ctx* c) {
@@ -196,27 +190,15 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
   c->sw = read_build_switches();
   // the reads are what the last correction left of the reads of the graph still held, nothing re-threaded: that graph's
   // live part IS the graph to build (amg_derive.hip; AMG_NO_DERIVE=1: A/B + test switch)
-  const bool derive = c->derive_ready && k == c->k && !c->dist_mode && !c->sw.no_derive;
-  c->derive_ready = c->dist_candidate = false;
-  c->derived = false;
-  c->built = false;
-  c->have_corrected = false;
-  c->match_valid = false;
-  c->retries = 0;
-  c->tok_base = 0;
-  c->tok_total = c->n_tokens;
+  // The derive stands between the two halves of "a build begins": it still needs the k and dist_mode of the graph at
+  // hand (to decide, and to squeeze that graph), and a derived graph keeps them
+  const bool derive = ctx_build_begins(c) && k == c->k && !c->dist_mode && !c->sw.no_derive;
   if (derive) {
     bool done = false;
     AMGCHK(derive_from_previous(c, k, &done));
     if (done) return AMG_OK;  // (amg_build_filtered goes on with amg_filter)
   }
-  c->k = k;
-  c->dist_mode = false;
-  c->comp_from_claims = false;
-  if (c->hint_bound > 0) {  // reads taken over from another ctx's correction: its bound holds for a graph at ITS gene-mer size
-    if (c->hint_bound_k == k) c->node_hint = c->hint_bound > 256 ? c->hint_bound : 256;
-    c->hint_bound = 0;
-  }
+  ctx_build_from_reads(c, k, false);
   // test hook: the first AMG_TEST_WEAK_FP attempts use a 12-bit fingerprint, which is
   // certain to collide; the exact verification must catch it and the retry must succeed
   c->weak_fp_builds = c->sw.weak_fp;
@@ -243,10 +225,8 @@ static int build_impl(amg_ctx* c, int32_t k, uint32_t min_node_cov, uint32_t min
     if (r == AMG_OK) r = bs_finish_from_pairs(c);
     if (r == AMG_OK && *fused) r = bx_flag_dead_reads(c);
     if (r == AMG_OK) {
-      c->built = true;
       // (a filtered build keeps only the survivors: the next table is sized by what the pass saw)
-      const int64_t seen = *fused ? c->n_local_nodes : c->n_nodes;
-      c->node_hint = seen > 256 ? seen : 256;
+      ctx_graph_in_place(c, *fused ? c->n_local_nodes : c->n_nodes, false);
       return AMG_OK;
     }
     if (r != AMG_E_OVERFLOW || which == OV_NONE) return r;
@@ -305,13 +285,7 @@ extern "C" int amg_build_multi(amg_ctx* const* ctxs, const int32_t* ks, int32_t 
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tokens.borrow(c0->tokens.p, (size_t)T * sizeof(int32_t));
     c->read_off.borrow(c0->read_off.p, (size_t)(R + 1) * sizeof(int64_t));
-    c->n_reads = R;
-    c->n_tokens = T;
-    c->two_v = c0->two_v;
-    c->have_pos = c->have_read_len = false;
-    c->node_hint = 0;
-    c->cnt_hint_reset = true;
-    c->derive_ready = c->dist_candidate = false;
+    ctx_reads_replaced(c, R, T, c0->two_v);
     c->stream = c0->stream;
   }
   struct Restore {

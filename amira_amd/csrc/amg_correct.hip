@@ -441,7 +441,9 @@ static int corr_pack(amg_ctx* c, const CorrScratch& S, const CorrArgs& a, const 
 // The call's last synchronisation; with it an upper bound for the nodes of the graph these reads will make (same k):
 // every window of a corrected read is a live node of this graph — untouched reads, slices, re-threaded paths —
 // except the dead windows of the reads that fell back to their original genes.
-static int corr_node_bound(amg_ctx* c, const CorrSwitches& sw, const CorrScratch& S, const CorrCounts& n) {
+// *only_drops_and_trims: no read was re-threaded or kept its genes around a dead window — reads were dropped or cut to their
+// live windows, so the graph they make is this graph's live part (amg_derive.hip) unless an edge died on its own
+static int corr_node_bound(amg_ctx* c, const CorrScratch& S, const CorrCounts& n, int64_t* bound_out, bool* only_drops_and_trims) {
   FetchList l;
   for (int i = 0; i < 16; ++i) l.add(S.dead_kept + 16 * i);
   l.add(S.dead_kept + 256);
@@ -450,13 +452,8 @@ static int corr_node_bound(amg_ctx* c, const CorrSwitches& sw, const CorrScratch
   unsigned long long bound = S.count_alive ? v[16] : (unsigned long long)c->n_nodes;
   unsigned long long dead_kept = 0;
   for (int i = 0; i < 16; ++i) dead_kept += v[i];
-  bound += dead_kept;
-  // the graph these reads will make is this graph's live part (amg_derive.hip) when no read was re-threaded or kept
-  // its genes around a dead window, and no edge died on its own: reads were dropped or cut to their live windows
-  c->c_derivable = n.n_gapped == 0 && dead_kept == 0 && !c->edge_own_deaths;
-  c->c_node_bound = (int64_t)bound;
-  if (sw.node_bound) c->c_node_bound = atoll(sw.node_bound);
-  c->c_node_bound_k = c->k;
+  *bound_out = (int64_t)(bound + dead_kept);
+  *only_drops_and_trims = n.n_gapped == 0 && dead_kept == 0;
   return AMG_OK;
 }
 
@@ -467,7 +464,7 @@ extern "C" int amg_correct_reads(amg_ctx* c, int64_t* n_out_reads, int64_t* n_ou
   NEED_BUILT(c);
   const CorrSwitches sw = read_switches();
   stages_reset(c);
-  c->have_corrected = false;
+  ctx_corrected_begun(c);
   CorrScratch S;
   CorrCounts n;
   CorrArgs a;
@@ -507,13 +504,13 @@ extern "C" int amg_correct_reads(amg_ctx* c, int64_t* n_out_reads, int64_t* n_ou
 
   stage_begin(c, "correct_pack");  // second interval: the pack itself
   AMGCHK(corr_pack(c, S, a, n));
-  AMGCHK(corr_node_bound(c, sw, S, n));
+  int64_t bound = 0;
+  bool only_drops_and_trims = false;
+  AMGCHK(corr_node_bound(c, S, n, &bound, &only_drops_and_trims));
   stage_end(c);
   if (sw.routes) AMGCHK(routes_end(c, n));
-  c->c_reads = n.out_reads;
-  c->c_tokens = n.out_tokens;
-  c->c_pos1_used = c->pos1_used + (n.carry ? n.pos_total : 0);  // becomes current with amg_adopt_corrected
-  c->have_corrected = true;
+  ctx_corrected_made(c, n.out_reads, n.out_tokens, c->pos1_used + (n.carry ? n.pos_total : 0), only_drops_and_trims, bound,
+                     sw.node_bound);
   if (n_out_reads) *n_out_reads = n.out_reads;
   if (n_out_tokens) *n_out_tokens = n.out_tokens;
   return AMG_OK;

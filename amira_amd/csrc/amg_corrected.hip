@@ -98,20 +98,14 @@ extern "C" int amg_set_positions32(amg_ctx* c, const int32_t* gene_start, const 
   if (T > 0)
     hipLaunchKernelGGL(k_widen_pos, dim3(nblk(T, 1024) < 4096u ? nblk(T, 1024) : 4096u), dim3(256), 0, st, d_s, d_e, T,
                        c->gene_start.as<long long>(), c->gene_end.as<long long>());
-  c->have_pos = true;
-  c->pos_identity = true;
-  c->pos0_own = false;
-  c->pos_n0 = T;
-  c->pos1_used = c->c_pos1_used = 0;
-  c->have_corrected = false;
-  c->have_read_len = false;
+  ctx_positions_replaced(c, T, false);
   if (read_len) {
     c->read_len.unborrow();
     AMGCHK(c->read_len.ensure((size_t)c->n_reads * sizeof(int64_t) + 64));
     if (c->n_reads > 0)
       HIPCHK(hipMemcpyAsync(c->read_len.p, read_len, (size_t)c->n_reads * sizeof(int64_t),
                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    c->have_read_len = true;
+    ctx_read_lengths_set(c);
   }
   HIPCHK(hipStreamSynchronize(st));
   return AMG_OK;
@@ -283,38 +277,16 @@ extern "C" int amg_adopt_corrected(amg_ctx* c) {
       c->gene_end.unborrow();
       std::swap(c->gene_start, c->c_gstart);
       std::swap(c->gene_end, c->c_gend);
-      compacted = true;
-      c->pos0_own = true;  // pool 0 is no longer what the caller handed over (amg_get_corrected32)
+      compacted = true;  // (pool 0 is no longer what the caller handed over)
     }
   }
   for (DevBuf* b : {&c->tokens, &c->read_off, &c->read_len}) b->unborrow();
   std::swap(c->tokens, c->c_tokens_buf);
   std::swap(c->read_off, c->c_read_off);
   std::swap(c->rd_src, c->c_src);
-  c->derive_ready = c->c_derivable;  // (the graph the reads were corrected against is still in place: amg_build may reuse it)
-  c->dist_candidate = c->dist_mode;  // (a rank of a merged build: the ranks decide together, amg_dist.hip S_DV_*)
-  c->c_derivable = false;
-  if (c->have_pos && compacted) {
-    c->pos_identity = true;
-    c->pos_n0 = c->c_tokens;
-    c->pos1_used = c->c_pos1_used = 0;
-  } else if (c->have_pos) {
-    std::swap(c->pos_off, c->c_pos_off);
-    c->pos_identity = false;
-    c->pos1_used = c->c_pos1_used;
-  }
+  if (c->have_pos && !compacted) std::swap(c->pos_off, c->c_pos_off);
   if (c->have_read_len) std::swap(c->read_len, c->c_read_len);
-  c->n_reads = c->c_reads;
-  c->n_tokens = c->c_tokens;
-  c->have_corrected = false;
-  c->built = false;
-  c->match_valid = false;
-  // the next build's node table: not larger than the correction's bound asks for (a graph of uncorrected reads is
-  // mostly error nodes that do not come back: 5.4 M nodes before, 0.5 M after on BASELINE config 3).  A build with
-  // another k, or a bound that does not hold, costs what any undersized table costs: one repeated pass.
-  if (c->c_node_bound > 0 && c->c_node_bound_k == c->k && (c->node_hint == 0 || c->c_node_bound < c->node_hint))
-    c->node_hint = c->c_node_bound > 256 ? c->c_node_bound : 256;
-  c->c_node_bound = 0;
+  ctx_corrected_adopted(c, compacted);
   return AMG_OK;
 }
 
@@ -334,10 +306,7 @@ extern "C" int amg_set_reads_from_corrected(amg_ctx* dst, amg_ctx* src) {
   AMGCHK(dst->read_off.ensure((size_t)(R + 1) * sizeof(int64_t) + 64));
   if (T > 0) HIPCHK(hipMemcpyAsync(dst->tokens.p, src->c_tokens_buf.p, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(dst->read_off.p, src->c_read_off.p, (size_t)(R + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-  dst->n_reads = R;
-  dst->n_tokens = T;
-  dst->two_v = src->two_v;
-  dst->have_pos = dst->have_read_len = false;
+  ctx_reads_replaced(dst, R, T, src->two_v);  // (dst has no graph of its own any more)
   if (src->have_pos) {
     AMGCHK(dst->gene_start.ensure((size_t)(T + 64) * sizeof(long long)));
     AMGCHK(dst->gene_end.ensure((size_t)(T + 64) * sizeof(long long)));
@@ -347,27 +316,17 @@ extern "C" int amg_set_reads_from_corrected(amg_ctx* dst, amg_ctx* src) {
                          src->c_pos_off.as<long long>(), R, dst->gene_start.as<long long>(),
                          dst->gene_end.as<long long>());
     }
-    dst->have_pos = true;
-    dst->pos0_own = true;  // gathered here: not arrays any caller holds
-    dst->pos_identity = true;
-    dst->pos_n0 = T;
-    dst->pos1_used = dst->c_pos1_used = 0;
+    ctx_positions_replaced(dst, T, true);  // gathered here: not arrays any caller holds
   }
   if (src->have_read_len) {
     AMGCHK(dst->read_len.ensure((size_t)(R + 1) * sizeof(long long) + 64));
     if (R > 0)
       HIPCHK(hipMemcpyAsync(dst->read_len.p, src->c_read_len.p, (size_t)R * sizeof(long long), hipMemcpyDeviceToDevice, st));
-    dst->have_read_len = true;
+    ctx_read_lengths_set(dst);
   }
   HIPCHK(hipStreamSynchronize(st));
-  dst->built = false;
-  dst->derive_ready = false;
-  dst->have_corrected = false;
-  dst->match_valid = false;
-  // (amg_adopt_corrected: the same bound — for a build at the gene-mer size it was made for; dst has no graph of its own)
-  dst->node_hint = 0;
+  // (amg_adopt_corrected: the same bound — for a build at the gene-mer size it was made for)
   dst->hint_bound = src->c_node_bound;
   dst->hint_bound_k = src->c_node_bound_k;
-  dst->cnt_hint_reset = true;
   return AMG_OK;
 }

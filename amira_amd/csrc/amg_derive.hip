@@ -296,9 +296,7 @@ int derive_commit(amg_ctx* c, long long D2, long long P2) {
   c->n_pairs = c->n_local_pairs = P2;
   c->comp_from_claims = false;  // (labels of the graph as it is now, made when somebody asks)
   AMGCHK(bs_finish_from_pairs(c));
-  c->built = true;
-  c->derived = true;
-  c->node_hint = D2 > 256 ? D2 : 256;
+  ctx_graph_in_place(c, D2, true);
   return AMG_OK;
 }
 

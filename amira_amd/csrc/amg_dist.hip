@@ -492,9 +492,7 @@ static Step st_dv_local(amg_ctx* c, DistState* d, amg_xfer* x) {
   // every rank squeezes its copy of the graph (when ITS correction allows it) and says so; only if all do is the
   // squeezed graph taken — otherwise the ordinary merged build runs, nothing it reads has been touched
   d->dv_ok = false;
-  const bool mine = c->derive_ready && (int)d->tokens.size() == W;
-  c->derive_ready = false;
-  c->dist_candidate = false;
+  const bool mine = ctx_take_derive_offer(c) && (int)d->tokens.size() == W;
   if (mine) {
     d->dv_bases.assign(W + 1, 0);
     for (int p = 0; p < W; ++p) d->dv_bases[p + 1] = d->dv_bases[p] + d->tokens[p];
@@ -599,7 +597,7 @@ extern "C" int amg_dist_merge_begin(amg_ctx* c, int32_t k, uint32_t min_node_cov
   // build: the ranks first find out whether that graph's live part will do (S_DV_*; AMG_NO_DERIVE=1: A/B + test switch)
   const bool candidate = c->dist_candidate && c->dist_mode && c->world == d->world && k == c->k && d->mn == 1 && d->me == 1 &&
                          !getenv("AMG_NO_DERIVE");  // (not c->sw: this build reads its switches later, in nodes_local)
-  if (!candidate) c->dist_candidate = c->derive_ready = false;
+  if (!candidate) (void)ctx_take_derive_offer(c);  // (declined; a candidate's offer is taken in st_dv_local)
   d->state = candidate ? S_DV_LOCAL : S_LOCAL;
   return AMG_OK;
 }

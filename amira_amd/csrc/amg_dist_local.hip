@@ -356,18 +356,9 @@ int nodes_local(amg_ctx* c, DistState* d) {
   const int k = d->k, world = d->world;
   stages_reset(c);
   c->sw = read_build_switches();  // (a merged build starts here)
-  c->built = false;
-  c->derive_ready = false;
-  c->derived = false;
-  c->have_corrected = false;
-  c->match_valid = false;
-  c->k = k;
-  c->retries = 0;
-  c->tok_base = 0;
-  c->tok_total = c->n_tokens;
+  (void)ctx_build_begins(c);  // (the offer of a derived rebuild was taken or declined before: amg_dist.hip)
+  ctx_build_from_reads(c, k, true);
   c->world = world;
-  c->dist_mode = true;
-  c->comp_from_claims = false;
   c->dist_min_node = d->mn;
   c->dist_min_edge = d->me;
   // merge keys and key owners are fingerprints of this seed: every rank must use the SAME one, whatever collision

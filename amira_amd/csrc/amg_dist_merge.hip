@@ -455,7 +455,6 @@ int edges_global(amg_ctx* c, DistState* d) {
     // fused filter: reads that lost a node join _readsToCorrect (remove_node_from_reads :442-461)
     AMGCHK(bx_flag_dead_reads(c));
   c->dist_min_node = c->dist_min_edge = 1;
-  c->built = true;
-  c->node_hint = c->n_local_nodes > 256 ? c->n_local_nodes : 256;
+  ctx_graph_in_place(c, c->n_local_nodes, false);
   return AMG_OK;
 }

@@ -175,10 +175,10 @@ static int st_walk_fold(amg_ctx* c, DistState* d, WalkState* w, amg_xfer*) {
     const long long D = c->n_nodes;
     const unsigned long long* all = wire ? w->recv.as<unsigned long long>() : w->send.as<unsigned long long>();
     AMGCHK(kill_marks_check(c, w->kept.marks));  // (the caller's exchanges ran since the local phase reserved them)
+    ctx_removal_begins(c);  // (here, not at the walk's begin: a walk that finds no node to trim on any rank keeps the set)
     stage_begin(c, "amr_trim_fold");
     hipLaunchKernelGGL(k_dw_fold_kill, dim3(nblk(D, 256)), dim3(256), 0, c->stream, all, W, n, c->node_alive.as<unsigned char>(), D,
                        w->kept.marks.bytes);
-    c->have_corrected = false;
     int64_t n_removed = 0;
     const int r = finish_kill(c, w->kept.marks, &n_removed, nullptr);
     stage_end(c);

@@ -116,6 +116,7 @@ static int apply_removals(amg_ctx* c, unsigned int min_edge_cov) {
 
 extern "C" int amg_filter(amg_ctx* c, uint32_t min_node_cov, uint32_t min_edge_cov) {
   NEED_BUILT(c);
+  ctx_removal_begins(c);
   stages_reset(c);
   stage_begin(c, "filter");
   if (c->n_nodes > 0)
@@ -124,7 +125,6 @@ extern "C" int amg_filter(amg_ctx* c, uint32_t min_node_cov, uint32_t min_edge_c
                        c->n_nodes, min_node_cov);
   AMGCHK(apply_removals(c, min_edge_cov));
   stage_end(c);
-  c->have_corrected = false;
   return AMG_OK;
 }
 
@@ -141,13 +141,13 @@ extern "C" int amg_remove_nodes(amg_ctx* c, const int32_t* node_ids, int64_t n) 
   NEED_BUILT(c);
   if (n < 0 || (n > 0 && !node_ids)) return amg_fail(AMG_E_ARG, "bad node list");
   if (n == 0) return AMG_OK;
+  ctx_removal_begins(c);
   AMGCHK(c->s0.ensure((size_t)n * sizeof(int)));
   HIPCHK(hipMemcpyAsync(c->s0.p, node_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_kill_listed, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->s0.as<int>(),
                      (long long)n, c->n_nodes, c->node_alive.as<unsigned char>());
   AMGCHK(apply_removals(c, 0));
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->have_corrected = false;
   return AMG_OK;
 }
 
@@ -158,13 +158,13 @@ extern "C" int amg_remove_edges(amg_ctx* c, const int32_t* edge_ids, int64_t n) 
   NEED_BUILT(c);
   if (n < 0 || (n > 0 && !edge_ids)) return amg_fail(AMG_E_ARG, "bad edge list");
   if (n == 0) return AMG_OK;
+  ctx_removal_begins(c);
   AMGCHK(c->s0.ensure((size_t)n * sizeof(int)));
   HIPCHK(hipMemcpyAsync(c->s0.p, edge_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_kill_listed, dim3(nblk(n, 256)), dim3(256), 0, c->stream, c->s0.as<int>(), (long long)n,
                      c->n_edges, c->edge_alive.as<unsigned char>());
   live_lists_after_edge_deaths(c);
   HIPCHK(hipStreamSynchronize(c->stream));
-  c->have_corrected = false;
   return AMG_OK;
 }
 
@@ -381,6 +381,7 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
   const long long D = c->n_nodes;
   if (n_removed) *n_removed = 0;
   if (D == 0) return AMG_OK;
+  ctx_removal_begins(c);
   stages_reset(c);
   // "a tip that is its whole component is kept" (:710-713) compares the path with the LIVE nodes of its component as
   // labelled at build time.  While nothing has been removed since the build that is the question whether a live edge
@@ -435,7 +436,6 @@ extern "C" int amg_remove_short_linear_paths(amg_ctx* c, int32_t min_length, con
   }
   int r = finish_kill(c, marks, n_removed, removed_ids);
   stage_end(c);
-  c->have_corrected = false;
   return r;
 }
 
@@ -452,6 +452,7 @@ extern "C" int amg_remove_low_coverage_components(amg_ctx* c, uint32_t min_cov) 
   hipStream_t st = c->stream;
   const long long D = c->n_nodes;
   if (D == 0) return AMG_OK;
+  ctx_removal_begins(c);
   AMGCHK(ensure_components(c));
   size_t nc = (size_t)(c->n_components + 2);
   KillMarks marks;
@@ -469,6 +470,5 @@ extern "C" int amg_remove_low_coverage_components(amg_ctx* c, uint32_t min_cov) 
                      (unsigned long long*)nullptr);
   hipLaunchKernelGGL(k_kill_low_components, dim3(nblk(D, 256)), dim3(256), 0, st, c->node_comp.as<int>(),
                      c->node_alive.as<unsigned char>(), high, D, marks.bytes);
-  c->have_corrected = false;
   return finish_kill(c, marks, nullptr, nullptr);
 }

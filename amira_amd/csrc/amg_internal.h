@@ -151,7 +151,7 @@ struct BubbleState;  // amg_bubbles.hip: what amg_junction_paths found, until th
 struct SketchState;  // amg_sketch.hip: the buffers of amg_path_sketch_overlaps
 struct PopState;     // amg_pop.hip: the buffers of amg_pop_rewrite
 
-// What ladj / ladj_rows hold (transitions: live_lists_after_*, ensure_live_adj; amg_live_rows.hip).
+// What ladj / ladj_rows hold (transitions: amg_state.h; ensure_live_adj, amg_live_rows.hip, makes the lists).
 // While the state is Absent, and only then, ladj_rows is free to hold tip clipping's row summary {live count, edge, edge,
 // -} (row_summary); making the summary leaves the state Absent.
 enum class LiveLists {
@@ -171,6 +171,8 @@ struct FpKeyList {
   long long n = 0;
 };
 
+// The flags that say what the ctx holds (built, have_*, pos_*, c_derivable, derive_ready, derived, dist_candidate,
+// edge_own_deaths, pristine, *_valid, live_lists, the hints) change in amg_state.h alone: its table is where the rules are
 struct amg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -200,9 +202,9 @@ struct amg_ctx {
   int64_t n_nodes = 0, n_pairs = 0, n_edges = 0, n_components = 0;
   int64_t node_slots = 0, edge_slots = 0, retries = 0;
   int64_t node_hint = 0;  // distinct-node estimate carried between builds
-  int64_t c_node_bound = 0;  // amg_correct_reads: upper bound for the nodes of the graph the corrected reads make (at gene-mer size c_node_bound_k)
+  int64_t c_node_bound = 0;  // upper bound for the nodes of the graph the corrected reads make (at gene-mer size c_node_bound_k)
   int c_node_bound_k = 0;
-  int64_t hint_bound = 0;    // amg_set_reads_from_corrected: the source's bound for THESE reads, applied by a build at hint_bound_k
+  int64_t hint_bound = 0;    // another ctx's such bound for THESE reads (at gene-mer size hint_bound_k)
   int hint_bound_k = 0;
   int64_t n_local_nodes = 0, n_local_pairs = 0;  // before a multi-GPU merge
   FpKeyList fp_keys;      // fingerprint path: the key list of the last table pass (n = n_local_nodes or n_local_pairs)
@@ -242,7 +244,7 @@ struct amg_ctx {
   DevBuf ladj_pos, ladj_keys;  // scratch of the live-adjacency build; it must never use the general scratch arrays, which its callers hold across it
   DevBuf hub_bits;             // bitmaps over the edge ids for adjacency rows beyond HUGE_ROW (huge_row_in_order, amg_rows.h)
   LiveLists live_lists = LiveLists::Absent;
-  bool comp_valid = false, adj_valid = false;  // component ids / full edge lists of the built graph are made on demand
+  bool comp_valid = false, adj_valid = false;  // component ids / full edge lists of the built graph have been made
   bool pristine = false;  // nothing has been removed since the build, and its component labels are those of the graph as it is
   // reads
   DevBuf read_fix;  // uint8[n_reads]  read is in _readsToCorrect
@@ -256,8 +258,8 @@ struct amg_ctx {
   // ---- the rebuild that reuses the previous build (amg_derive.hip)
   DevBuf c_src, rd_src;          // int64[reads]: token index, in the read set the graph was built from, of every corrected /
                                  // current read's first gene
-  bool c_derivable = false;      // amg_correct_reads: the corrected set only drops and trims reads of the graph's read set
-  bool derive_ready = false;     // the current reads are such a set of the graph still held (amg_adopt_corrected)
+  bool c_derivable = false;      // the corrected set only drops and trims reads of the graph's read set
+  bool derive_ready = false;     // the current reads are such a set of the graph still held
   bool derived = false;          // the graph at hand was made that way (amg_counts)
   bool dist_candidate = false;   // the same on a rank of a merged build, whatever THIS rank's correction did (every rank asks)
   bool edge_own_deaths = false;  // since the build an edge was removed with both its nodes alive
@@ -437,10 +439,6 @@ struct GView {
 };
 int ensure_live_adj(amg_ctx* c);  // the live lists below exist and are up to date
 GView make_view(amg_ctx* c);
-// what happened to the graph, as far as its live lists (and pristine, edge_own_deaths, match_valid) are concerned
-void live_lists_after_node_deaths(amg_ctx* c);  // nodes died, and every edge that died has a dead end
-void live_lists_after_edge_deaths(amg_ctx* c);  // an edge died with both its ends alive
-void live_lists_after_build(amg_ctx* c);        // a new graph
 // Kill marks (amg_filter.hip): a byte per node, non-zero = the node is to die.  kill_marks_reserve hands them out and puts
 // their n + 8 bytes on the caller's ClearList, so they are zero once that list has been cleared; the caller's kernels mark
 // through the value; finish_kill uses it up.  Between the two nothing else may reserve marks on the ctx.
@@ -559,3 +557,5 @@ static inline int ilog2_ceil(uint64_t x) {
   while ((1ull << b) < x && b < 63) ++b;
   return b;
 }
+
+#include "amg_state.h"  // the transitions of the flags above, one per event

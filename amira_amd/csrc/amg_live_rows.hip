@@ -1,30 +1,9 @@
 // amg_live_rows.hip — the adjacency of the LIVE edges, which every walker reads (tip clipping, the re-threading search
-// of the correction, the junction search of bubble popping: GView, amg_internal.h): its lists (ensure_live_adj), what a
-// removal or a build does to them (live_lists_after_*), and tip clipping's one-pass row summary where no lists exist
-// (row_summary).  The removals themselves are amg_filter.hip's; the full lists of the graph as built are
+// of the correction, the junction search of bubble popping: GView, amg_internal.h): its lists (ensure_live_adj) and tip clipping's
+// one-pass row summary where no lists exist (row_summary).  What a removal or a build does to the lists' state
+// (LiveLists): amg_state.h.  The removals themselves are amg_filter.hip's; the full lists of the graph as built are
 // amg_adjacency.hip's; a row's ids are put in order by amg_rows.h.
 #include "amg_rows.h"
-
-// ------------------------------------------------------------------ the state of the lists (LiveLists, amg_internal.h)
-// nodes died, and every edge that died with them has a dead end: lists that exist are kept and brought up to date
-// (k_lr_patch) when somebody walks them again (AMG_NO_LADJ_PATCH=1: they are made again; A/B + test switch)
-void live_lists_after_node_deaths(amg_ctx* c) {
-  if (c->live_lists == LiveLists::Current)
-    c->live_lists = getenv("AMG_NO_LADJ_PATCH") ? LiveLists::Absent : LiveLists::BehindNodes;
-  c->pristine = false;
-  c->match_valid = false;  // node-id patterns of a cached K6 result may name removed nodes
-}
-
-// an edge died with both its ends alive (a coverage threshold above 1, amg_remove_edges): the lists are made again
-void live_lists_after_edge_deaths(amg_ctx* c) {
-  c->live_lists = LiveLists::Absent;
-  c->edge_own_deaths = true;
-  c->pristine = false;
-  c->match_valid = false;
-}
-
-// a new build: there are no lists of this graph
-void live_lists_after_build(amg_ctx* c) { c->live_lists = LiveLists::Absent; }
 
 // ------------------------------------------------------------------ the lists from the live edges
 // One scan over the edges' alive bytes squeezes the removed edges out in edge order: its emitter writes the dense list of
@@ -181,7 +160,7 @@ int ensure_live_adj(amg_ctx* c) {
   if (c->live_lists == LiveLists::BehindNodes) {
     hipLaunchKernelGGL(k_lr_patch, dim3(nblk(2 * c->n_nodes, 256)), dim3(256), 0, st, c->ladj_rows.as<int4>(),
                        c->ladj.as<int2>(), 2 * c->n_nodes, c->node_alive.as<unsigned char>());
-    c->live_lists = LiveLists::Current;
+    live_lists_made(c);
     return AMG_OK;
   }
   const long long rows = 2 * c->n_nodes, E = c->n_edges;
@@ -224,7 +203,7 @@ int ensure_live_adj(amg_ctx* c) {
                        c->edge_tdir.as<signed char>(), c->ladj_rows.as<int4>(), c->ladj.as<int2>(),
                        c->hub_bits.as<unsigned int>(), hub_words);
   }
-  c->live_lists = LiveLists::Current;
+  live_lists_made(c);
   return AMG_OK;
 }
 

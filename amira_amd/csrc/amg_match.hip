@@ -198,7 +198,7 @@ extern "C" int amg_match_patterns(amg_ctx* c, int which, const int32_t* pat, con
     HIPCHK(hipStreamSynchronize(st));
     return AMG_OK;
   }
-  c->match_valid = false;
+  ctx_match_begun(c);
   stages_reset(c);
   if (n_pat >= (1ll << PAT_BITS)) return amg_fail(AMG_E_ARG, "at most %d patterns per call", (1 << PAT_BITS) - 1);
   if (c->n_reads >= (1ll << READ_BITS)) return amg_fail(AMG_E_ARG, "too many reads for amg_match_patterns");

@@ -503,6 +503,7 @@ extern "C" int amg_remove_non_amr_nodes(amg_ctx* c, const uint8_t* gene_flags, i
   *n_removed = 0;
   const long long D = c->n_nodes;
   if (D == 0) return AMG_OK;
+  ctx_removal_begins(c);
   stages_reset(c);
   stage_begin(c, "amr_trim");
   std::vector<unsigned int> words;
@@ -510,7 +511,6 @@ extern "C" int amg_remove_non_amr_nodes(amg_ctx* c, const uint8_t* gene_flags, i
   AMGCHK(rw_keep_local(c, gene_flags, &words, &kept));
   hipLaunchKernelGGL(k_rw_kill_unkept, dim3(nblk(D, 256)), dim3(256), 0, c->stream, c->node_alive.as<unsigned char>(),
                      kept.keep, D, kept.marks.bytes);
-  c->have_corrected = false;
   const int r = finish_kill(c, kept.marks, n_removed, nullptr);  // (waits for the stream: `words` has been taken)
   stage_end(c);
   return r;

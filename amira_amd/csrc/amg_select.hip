@@ -190,8 +190,7 @@ extern "C" int amg_select_reads(amg_ctx* c, int32_t mode, int32_t invert, const 
   hipStream_t st = c->stream;
   const long long R = c->n_reads, T = c->n_tokens;
   stages_reset(c);
-  c->have_corrected = false;
-  c->c_derivable = false;
+  ctx_corrected_begun(c);
 
   // scratch: verdicts; keep flags and lengths; the two scans; the table; the counters [16 x 16 words], alive nodes
   // and the most windows behind them
@@ -285,13 +284,7 @@ extern "C" int amg_select_reads(amg_ctx* c, int32_t mode, int32_t invert, const 
   // masked windows (an upper bound: masked windows may share a node)
   unsigned long long bound = v[18];
   for (int i = 0; i < 16; ++i) bound += v[2 + i];
-  c->c_node_bound = (int64_t)bound;
-  if (const char* e = getenv("AMG_TEST_NODE_BOUND")) c->c_node_bound = atoll(e);
-  c->c_node_bound_k = c->k;
-  c->c_reads = (int64_t)v[0];
-  c->c_tokens = (int64_t)v[1];
-  c->c_pos1_used = c->pos1_used;
-  c->have_corrected = true;
+  ctx_corrected_made(c, (int64_t)v[0], (int64_t)v[1], c->pos1_used, false, (int64_t)bound, getenv("AMG_TEST_NODE_BOUND"));
   if (n_out_reads) *n_out_reads = c->c_reads;
   if (n_out_tokens) *n_out_tokens = c->c_tokens;
   return AMG_OK;
