@@ -21,6 +21,7 @@ struct CorrArgs {
   const int* tok_node;
   const signed char* tok_dir;
   const unsigned char* read_fix;
+  const unsigned long long* win_mask;  // live windows 0..63 per read from the last removal's read walk; null: not current
   // gene positions are NOT moved with the genes when reads are corrected: a read carries an offset
   // (pos_off[r]; nullptr = its token offset) into one of two pools — the caller's arrays as handed to
   // amg_set_positions (indices < n0) or the positions the carry-over kernels produced (p1*, indices
@@ -37,7 +38,7 @@ struct CorrArgs {
   int k, flip, have_pos;
   // per read
   unsigned int* gflag;            // 1: the read is re-threaded (RC_GAPPED)
-  unsigned long long* max_bound;  // largest `bound` of a re-threaded read
+  unsigned long long* max_bound;  // largest `bound` of a re-threaded read: 16 partial maxima, 16 words apart
   unsigned long long* lmask;      // live-window mask of a flagged read with <= 64 windows (0 otherwise)
   unsigned long long* n_runs;     // None runs over all re-threaded reads: 16 partial sums, 16 words apart
   unsigned char* cls;
@@ -263,10 +264,10 @@ struct CorrScratch {
   int* tmp_tok = nullptr;                                                    // staged genes of the re-threaded reads
   long long *plen = nullptr, *poffs = nullptr, *pos_new = nullptr;           // (carry-over only): per gapped read new
                                                                              // positions + prefix, per read its pool index
-  // counters.  ST_MISC of the status words has two lives: the largest staging bound until the classify step's
-  // fetch, the number of reads for the general carry-over kernel from k_nw_sizes on
-  unsigned long long *max_bound = nullptr, *n_general = nullptr;
+  // counters.  ST_MISC of the status words: the number of reads for the general carry-over kernel (k_nw_sizes)
+  unsigned long long* n_general = nullptr;
   unsigned long long* n_runs = nullptr;     // gm_ctr + 16: [16 x 16 words] ([0, 16) belong to the path memo)
+  unsigned long long* max_bound = nullptr;  // n_runs + 8: the largest staging bound, a partial maximum beside each partial sum
   unsigned long long* dead_kept = nullptr;  // n_runs + 256: [16 x 16 words] (k_corr_pack), then the live nodes
   bool count_alive = false;                 // k_count_alive rides along (large graphs: the next build's table)
   // OUTPUT buffers of the correction that serve as scratch under these names until the shape step is over and

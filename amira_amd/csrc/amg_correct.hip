@@ -3,7 +3,10 @@
 //
 // Pipeline (all device; the host reads a few words back between the steps to size what comes next):
 //   classify   k_corr_classify: a wave per 64 reads, a read per lane.  Flagged reads with <= 64 windows are judged on
-//              a live-window mask (kept in gm_mask for the steps below), longer ones are walked by the wave.  Class,
+//              a live-window mask (kept in gm_mask for the steps below), longer ones are walked by the wave.  The mask
+//              comes from win_mask, where the read walk of the last removal (k_mask_reads, amg_filter.hip) left one for
+//              every read, while those masks are current (WindowMasks, amg_state.h); after anything else has written
+//              tok_node or read_fix — a filtered build's own flags — it is balloted from the read's windows.  Class,
 //              [start, end] (find_read_boundaries :1153-1164), None runs inside (identify_path_terminals :1375-1386);
 //              unmarked reads are copies, reads that only lost their ends are slices ([start : end + k], :1277-1285);
 //              reads with None runs are RC_GAPPED and get a staging bound.  One scan pair: staging offsets, gapped list.
@@ -28,17 +31,19 @@
 
 // live nodes of the graph the reads were corrected against (with PackArgs::dead_kept: an upper bound for the nodes of
 // the graph the corrected reads will make)
+#define COUNT_PER 16
 __global__ __launch_bounds__(256) void k_count_alive(const unsigned char* __restrict__ alive, long long n,
                                                      unsigned long long* out) {
+  // a grid sized to the array, COUNT_PER bytes a thread in one 16-byte load: 128 grid-stride workgroups had ten loads of
+  // four bytes a thread in a row and waited for each (18 us for 5.4 MB)
   __shared__ unsigned int s_part[4];
   unsigned int c = 0;
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * blockDim.x * 4) {
-    if (i + 4 <= n) {
-      const unsigned int w = *reinterpret_cast<const unsigned int*>(alive + i);  // (flags are 0 / 1 bytes)
-      c += __popc(w & 0x01010101u);
-    } else {
-      for (long long j = i; j < n; ++j) c += alive[j] ? 1u : 0u;
-    }
+  const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * COUNT_PER;
+  if (i + COUNT_PER <= n) {
+    const uint4 w = *reinterpret_cast<const uint4*>(alive + i);  // (flags are 0 / 1 bytes)
+    c = __popc(w.x & 0x01010101u) + __popc(w.y & 0x01010101u) + __popc(w.z & 0x01010101u) + __popc(w.w & 0x01010101u);
+  } else {
+    for (long long j = i; j < n; ++j) c += alive[j] ? 1u : 0u;
   }
   for (int d = 32; d > 0; d >>= 1) c += (unsigned int)__shfl_xor((int)c, d, 64);
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
@@ -55,8 +60,7 @@ __global__ __launch_bounds__(256) void k_count_alive(const unsigned char* __rest
 // stored every result with its own one-lane instruction: ~8 vector-memory instructions per read.)
 __global__ __launch_bounds__(256) void k_corr_classify(CorrArgs a) {
   const long long rbase = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * CLS_READS;
-  if (rbase >= a.n_reads) return;
-  const int lane = threadIdx.x & 63;
+  const int lane = threadIdx.x & 63;  // (a wave past the last read stays, with no read in any lane: the barrier below)
   const long long r = rbase + lane;
   const bool have = r < a.n_reads;
   const long long t0 = have ? a.read_off[r] : 0;
@@ -64,7 +68,11 @@ __global__ __launch_bounds__(256) void k_corr_classify(CorrArgs a) {
   const bool look = have && n > 0 && a.read_fix[r] != 0;
   // live-window masks of the flagged reads with <= 64 windows
   unsigned long long lv = 0;
-  unsigned long long todo = __ballot(look && n <= 64);
+  // ... as the removal's read walk left them (win_mask: current masks of tok_node as it stands, one per lane like the
+  // read's other inputs; bits from the window count on are masked off, whatever the tokens behind the last window hold)
+  if (a.win_mask && look && n <= 64) lv = a.win_mask[r] & (n == 64 ? ~0ull : (1ull << n) - 1ull);
+  // ... or, without current masks (flags of a filtered build), from the windows themselves
+  unsigned long long todo = a.win_mask ? 0ull : __ballot(look && n <= 64);
   while (todo) {
     int who[4];
     long long tj[4];
@@ -165,8 +173,12 @@ __global__ __launch_bounds__(256) void k_corr_classify(CorrArgs a) {
     a.gflag[r] = cls == RC_GAPPED ? 1u : 0u;  // list of re-threaded reads (scan input)
     a.lmask[r] = (cls == RC_GAPPED && n <= 64) ? lv : 0ull;
   }
-  // largest staging bound of a re-threaded read and the number of None runs: one atomic per wave each (the maximum
-  // only when it raises a plain — possibly stale, never too large — read of it); lanes past the last read hold zeros
+  // largest staging bound of a re-threaded read and the number of None runs: one atomic per WORKGROUP each, on 16
+  // words 128 bytes apart (one word takes ~90 atomics per microsecond).  With the masks at hand the waves of a million
+  // reads get here within a few microseconds of each other: a maximum on ONE word, guarded by a plain read of it that
+  // every wave made before any atomic had landed, queued 15 000 atomics there (160 us).  Lanes past the last read hold
+  // zeros.
+  __shared__ unsigned int s_mb[4], s_nr[4];
   unsigned int mb = (have && cls == RC_GAPPED) ? bound : 0u;
   unsigned int nr = (have && cls == RC_GAPPED) ? runs : 0u;
   for (int d = 32; d > 0; d >>= 1) {
@@ -174,9 +186,17 @@ __global__ __launch_bounds__(256) void k_corr_classify(CorrArgs a) {
     mb = mb > o ? mb : o;
     nr += (unsigned int)__shfl_xor((int)nr, d, 64);
   }
-  if (lane == 0 && (unsigned long long)mb > *a.max_bound) atomicMax(a.max_bound, (unsigned long long)mb);
-  // (16 counter words 128 bytes apart: one word takes ~90 atomics per microsecond, a wave per 64 reads asks more)
-  if (lane == 0 && nr) atomicAdd(a.n_runs + 16 * (blockIdx.x & 15), (unsigned long long)nr);
+  if (lane == 0) {
+    s_mb[threadIdx.x >> 6] = mb;
+    s_nr[threadIdx.x >> 6] = nr;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned int m01 = s_mb[0] > s_mb[1] ? s_mb[0] : s_mb[1], m23 = s_mb[2] > s_mb[3] ? s_mb[2] : s_mb[3];
+    const unsigned int m = m01 > m23 ? m01 : m23, s = s_nr[0] + s_nr[1] + s_nr[2] + s_nr[3];
+    if (m) atomicMax(a.max_bound + 16 * (blockIdx.x & 15), (unsigned long long)m);
+    if (s) atomicAdd(a.n_runs + 16 * (blockIdx.x & 15), (unsigned long long)s);
+  }
 }
 
 // One wave packs 64 consecutive reads.  Lane l owns read l's record: where its genes come from (the read itself,
@@ -291,8 +311,9 @@ static int plan_per_read(amg_ctx* c, CorrScratch& S) {
   S.tmp_off = c->s3.as<long long>();
   S.new_idx = S.tmp_off + per_read;
   S.new_off = S.new_idx + per_read;
-  S.max_bound = S.n_general = c->status.as<unsigned long long>() + ST_MISC;
+  S.n_general = c->status.as<unsigned long long>() + ST_MISC;
   S.n_runs = c->gm_ctr.as<unsigned long long>() + 16;
+  S.max_bound = S.n_runs + 8;  // (the other half of each partial sum's 128 bytes)
   S.dead_kept = S.n_runs + 256;
   S.count_alive = c->n_nodes >= (1ll << 20);
   S.glist = &c->c_orig;
@@ -325,6 +346,7 @@ static void corr_args(amg_ctx* c, const CorrScratch& S, CorrArgs& a) {
   a.tok_node = c->tok_node.as<int>();
   a.tok_dir = c->tok_dir.as<signed char>();
   a.read_fix = c->read_fix.as<unsigned char>();
+  a.win_mask = c->win_masks == WindowMasks::Current ? c->win_mask.as<unsigned long long>() : nullptr;
   fill_pos_args(c, a);
   a.read_len = c->have_read_len ? c->read_len.as<long long>() : nullptr;
   a.n_reads = c->n_reads;
@@ -353,28 +375,27 @@ static int corr_classify(amg_ctx* c, const CorrScratch& S, const CorrArgs& a, Co
   {
     ClearList cl;
     cl.add(S.bound, S.per_read * sizeof(unsigned int) * 3);
-    cl.add(S.max_bound, sizeof(unsigned long long));
-    cl.add(S.n_runs, (256 + 256 + 16) * sizeof(unsigned long long));
+    cl.add(S.n_runs, (256 + 256 + 16) * sizeof(unsigned long long));  // (the partial maxima lie between the sums)
     AMGCHK(clear_many(c, cl));
   }
   if (R > 0) hipLaunchKernelGGL(k_corr_classify, dim3(nblk(R, 4 * CLS_READS)), dim3(256), 0, st, a);  // also new_len, flag, max
   // (for the next build's table: how many nodes are alive; rides along, read back with the pack step's words)
   if (S.count_alive)
-    hipLaunchKernelGGL(k_count_alive, dim3(128), dim3(256), 0, st, c->node_alive.as<unsigned char>(), c->n_nodes,
+    hipLaunchKernelGGL(k_count_alive, dim3(nblk(c->n_nodes, 256 * COUNT_PER)), dim3(256), 0, st, c->node_alive.as<unsigned char>(), c->n_nodes,
                        S.dead_kept + 256);
   // where the re-threaded reads' genes are staged, and the list of gapped reads: two scans, one launch
   AMGCHK(prim_exscan_u32_pair(c, S.bound, S.tmp_off, S.flag, S.new_idx, (size_t)R));
   FetchList l;
   l.add(S.tmp_off + R);
-  l.add(S.max_bound);
   l.add(S.new_idx + R);
   for (int i = 0; i < 16; ++i) l.add(S.n_runs + 16 * i);
-  unsigned long long v[3 + 16];
+  for (int i = 0; i < 16; ++i) l.add(S.max_bound + 16 * i);
+  unsigned long long v[2 + 16 + 16];
   AMGCHK(fetch(c, l, v));
   n.tmp_total = (long long)v[0];
-  n.max_bound = v[1];
-  n.n_gapped = (long long)v[2];
-  for (int i = 0; i < 16; ++i) n.total_runs += (long long)v[3 + i];
+  n.n_gapped = (long long)v[1];
+  for (int i = 0; i < 16; ++i) n.total_runs += (long long)v[2 + i];
+  for (int i = 0; i < 16; ++i) n.max_bound = n.max_bound > v[18 + i] ? n.max_bound : v[18 + i];
   n.carry = n.n_gapped > 0 && c->have_pos;
   return AMG_OK;
 }

@@ -5,10 +5,28 @@
 
 // ------------------------------------------------------------------ filter_graph (:523-540)
 // list_nodes_to_remove (:496-503): coverage < minNodeCoverage
-__global__ void k_filter_nodes(const unsigned int* __restrict__ cov, unsigned char* __restrict__ alive,
-                               long long n, unsigned int min_cov) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && alive[i] && cov[i] < min_cov) alive[i] = 0;
+// Four nodes a thread, k_filter_edges' form below (the node arrays are allocations of their own): the alive bytes arrive
+// as one word, the coverages as 16 bytes, the four bytes leave as one word where one of them changed; a quad with
+// nothing alive returns after the first load, the last n mod 4 nodes take the scalar form.
+__global__ __launch_bounds__(256) void k_filter_nodes(const unsigned int* __restrict__ cov, unsigned char* __restrict__ alive,
+                                                      long long n, unsigned int min_cov) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long i0 = 4 * q;
+  if (i0 >= n) return;
+  if (i0 + 4 > n) {
+    for (long long i = i0; i < n; ++i)
+      if (alive[i] && cov[i] < min_cov) alive[i] = 0;
+    return;
+  }
+  const unsigned int a = reinterpret_cast<const unsigned int*>(alive)[q];
+  if (a == 0u) return;
+  const uint4 c = reinterpret_cast<const uint4*>(cov)[q];
+  unsigned int keep = 0u;
+  if (c.x >= min_cov) keep |= 0x000000ffu;
+  if (c.y >= min_cov) keep |= 0x0000ff00u;
+  if (c.z >= min_cov) keep |= 0x00ff0000u;
+  if (c.w >= min_cov) keep |= 0xff000000u;
+  if ((a & keep) != a) reinterpret_cast<unsigned int*>(alive)[q] = a & keep;
 }
 
 // list_edges_to_remove (:505-521): coverage < minEdgeCoverage or a doomed endpoint
@@ -66,7 +84,8 @@ __global__ __launch_bounds__(256) void k_mask_reads(int* __restrict__ tok_node,
                                                     const long long* __restrict__ read_off,
                                                     long long n_reads,
                                                     const unsigned char* __restrict__ node_alive,
-                                                    unsigned char* __restrict__ read_fix) {
+                                                    unsigned char* __restrict__ read_fix,
+                                                    unsigned long long* __restrict__ win_mask) {
   const long long rbase = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * READS_PER_WAVE;
   if (rbase >= n_reads) return;
   const int lane = threadIdx.x & 63;
@@ -83,6 +102,16 @@ __global__ __launch_bounds__(256) void k_mask_reads(int* __restrict__ tok_node,
   bool dead[READS_PER_WAVE];
 #pragma unroll
   for (int j = 0; j < READS_PER_WAVE; ++j) dead[j] = v[j] >= 0 && !node_alive[v[j]];
+  // The live windows 0..63 of every read walked, flagged now or by an earlier removal or not at all, as tok_node reads
+  // once this kernel is through (WindowMasks: k_corr_classify takes them instead of loading the windows again); tokens
+  // past a read's last window hold -1.  Lane j keeps read j's mask: one 64-byte store per wave.
+  unsigned long long mine = 0;
+#pragma unroll
+  for (int j = 0; j < READS_PER_WAVE; ++j) {
+    const unsigned long long m = __ballot(v[j] >= 0 && !dead[j]);
+    if (lane == j) mine = m;
+  }
+  if (lane < READS_PER_WAVE && rbase + lane < n_reads) win_mask[rbase + lane] = mine;
 #pragma unroll
   for (int j = 0; j < READS_PER_WAVE; ++j) {
     if (dead[j]) tok_node[a[j] + lane] = -2;
@@ -107,10 +136,13 @@ static int apply_removals(amg_ctx* c, unsigned int min_edge_cov) {
                        c->edge_src.as<int>(), c->edge_tgt.as<int>(), c->edge_cov.as<unsigned int>(),
                        c->node_alive.as<unsigned char>(), c->edge_alive.as<unsigned char>(),
                        c->n_edges, min_edge_cov);
+  AMGCHK(c->win_mask.ensure((size_t)(c->n_reads + 2) * sizeof(unsigned long long)));
   if (c->n_reads > 0)
     hipLaunchKernelGGL(k_mask_reads, dim3(nblk(c->n_reads, 4 * READS_PER_WAVE)), dim3(256), 0, st,
                        c->tok_node.as<int>(), c->read_off.as<long long>(), c->n_reads,
-                       c->node_alive.as<unsigned char>(), c->read_fix.as<unsigned char>());
+                       c->node_alive.as<unsigned char>(), c->read_fix.as<unsigned char>(),
+                       c->win_mask.as<unsigned long long>());
+  window_masks_made(c);  // (every read was walked: a read flagged by an earlier removal has its mask of now)
   return AMG_OK;
 }
 
@@ -120,7 +152,7 @@ extern "C" int amg_filter(amg_ctx* c, uint32_t min_node_cov, uint32_t min_edge_c
   stages_reset(c);
   stage_begin(c, "filter");
   if (c->n_nodes > 0)
-    hipLaunchKernelGGL(k_filter_nodes, dim3(nblk(c->n_nodes, 256)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_filter_nodes, dim3(nblk(c->n_nodes, 4 * 256)), dim3(256), 0, c->stream,
                        c->node_cov.as<unsigned int>(), c->node_alive.as<unsigned char>(),
                        c->n_nodes, min_node_cov);
   AMGCHK(apply_removals(c, min_edge_cov));

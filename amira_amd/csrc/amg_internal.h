@@ -160,6 +160,14 @@ enum class LiveLists {
   BehindNodes,  // the lists of the graph before some NODES died (no edge died with both ends alive): k_lr_patch brings them up to date
 };
 
+// What win_mask holds (transitions: amg_state.h).  k_mask_reads (amg_filter.hip) leaves, for every read, the ballot of its
+// first 64 windows that name a live node; k_corr_classify takes a flagged read's mask from there instead of loading the
+// windows again — while the masks describe tok_node as it stands.
+enum class WindowMasks {
+  Absent,   // tok_node / read_fix were written by something else since (a build, a derive, new reads) or never masked
+  Current,  // the masks of tok_node as it is: the last writer of tok_node was k_mask_reads, over every read
+};
+
 // The key list of a table pass on the fingerprint path (amg_build_fp.hip): (first_seen, slot) of the table's n occupied
 // slots in any order, and where fp_list_sort puts them in first-seen order.  Device pointers into the ctx's scratch: the
 // list holds from the pass that made it (bs_nodes_pass, bs_edges_pass) to the one consumer that follows it.
@@ -248,6 +256,8 @@ struct amg_ctx {
   bool pristine = false;  // nothing has been removed since the build, and its component labels are those of the graph as it is
   // reads
   DevBuf read_fix;  // uint8[n_reads]  read is in _readsToCorrect
+  DevBuf win_mask;  // uint64[n_reads] live windows 0..63 of every read as k_mask_reads last saw them (WindowMasks)
+  WindowMasks win_masks = WindowMasks::Absent;
 
   // ---- corrected read set (output of amg_correct_reads)
   bool have_corrected = false;

@@ -21,6 +21,7 @@
 //  comp_valid, adj_valid                                                                               cleared
 //  match_valid     cleared                                             cleared    cleared                                  cleared    cleared
 //  live_lists                                                                                          Absent              from (6)   Absent   Current
+//  win_masks       Absent                                              Absent     Absent               Absent              (11)
 //  cnt_hint_reset  set
 //  node_hint       0                                                   from (7)            from (8)    from (9)
 //  hint_bound      0 (10)                                                                  0 (8)
@@ -36,6 +37,8 @@
 //  (8) single build only: hint_bound where it was made for this k, at least 256, and used up
 //  (9) the nodes the build saw, at least 256
 //  (10) amg_set_reads_from_corrected then sets hint_bound / hint_bound_k from the source's c_node_bound
+//  (11) a removal's read walk (k_mask_reads over every read, apply_removals) makes them Current: window_masks_made; a
+//      removal that walks no reads (amg_remove_edges, a clip that finds nothing) leaves them as they are
 //  And: a new search of amg_match_patterns clears match_valid (ctx_match_begun); amg_count.hip takes cnt_hint_reset.
 #pragma once
 #include <cstdlib>
@@ -43,6 +46,13 @@
 #include "amg_internal.h"
 
 static inline int64_t ctx_hint_floor(int64_t n) { return n > 256 ? n : 256; }
+
+// ---- 0. the live-window masks of the reads (WindowMasks, amg_internal.h).  Made by the read walk of a removal, which
+// visits every read and is then the last writer of tok_node; void as soon as anything else writes tok_node or read_fix
+// or the reads change: new reads, an adopted correction, a build from its first step (tok_node is scratch of a merged
+// build's node pass) to the graph in place (plain, filtered — whose dead-read flags have no masks —, merged, derived)
+static inline void window_masks_made(amg_ctx* c) { c->win_masks = WindowMasks::Current; }
+static inline void window_masks_void(amg_ctx* c) { c->win_masks = WindowMasks::Absent; }
 
 // ---- 1. a read set arrives from outside (amg_set_reads, amg_build_multi's borrowers, amg_set_reads_from_corrected's dst)
 static inline void ctx_reads_replaced(amg_ctx* c, int64_t n_reads, int64_t n_tokens, int32_t two_v) {
@@ -52,6 +62,7 @@ static inline void ctx_reads_replaced(amg_ctx* c, int64_t n_reads, int64_t n_tok
   c->derive_ready = c->dist_candidate = false;
   c->node_hint = c->hint_bound = 0;
   c->cnt_hint_reset = true;  // what the counting sweeps learned belongs to the previous read set
+  window_masks_void(c);
 }
 
 // ---- 2. positions arrive.  own: pool 0 is the engine's own gather, not arrays a caller holds (amg_get_corrected32)
@@ -93,6 +104,7 @@ static inline void ctx_corrected_adopted(amg_ctx* c, bool compacted) {
   }
   c->n_reads = c->c_reads, c->n_tokens = c->c_tokens;
   c->c_derivable = c->have_corrected = c->built = c->match_valid = false;
+  window_masks_void(c);
   // the next build's node table: not larger than the correction's bound asks for (a graph of uncorrected reads is
   // mostly error nodes that do not come back: 5.4 M nodes before, 0.5 M after on BASELINE config 3).  A build with
   // another k, or a bound that does not hold, costs what any undersized table costs: one repeated pass.
@@ -114,6 +126,7 @@ static inline bool ctx_build_begins(amg_ctx* c) {
   c->derived = c->built = c->have_corrected = c->match_valid = false;
   c->retries = c->tok_base = 0;
   c->tok_total = c->n_tokens;
+  window_masks_void(c);
   return ctx_take_derive_offer(c);
 }
 // ... and goes on from the reads (no derive, or the derive declined)
@@ -131,6 +144,7 @@ static inline void ctx_build_from_reads(amg_ctx* c, int32_t k, bool merged) {
 // of a filtered build those before its filter: the next table is sized by what the pass meets
 static inline void ctx_graph_in_place(amg_ctx* c, int64_t seen, bool derived) {
   c->live_lists = LiveLists::Absent;  // there are no lists of this graph
+  window_masks_void(c);               // ... and no masks of its tok_node
   c->pristine = !c->comp_from_claims;
   c->edge_own_deaths = c->comp_valid = c->adj_valid = false;
   c->n_components = 0;
