@@ -274,24 +274,15 @@ def test_edge_classes_of_single_nodes(lone, shards, monkeypatch):
     nobody took in between), which large inputs use."""
     import token_oracle
     from amira_amd import Engine
+    from key_layouts import EDGE_CLASS_CASES, edge_class_reads
     monkeypatch.setenv("AMG_EDGE_LONE", lone)
     monkeypatch.setenv("AMG_CLAIM_SHARDS", shards)
     if lone == shards == "1":  # and with a head launch: the first tiles take their claims densely from a counter of their own
         monkeypatch.setenv("AMG_X_HEAD_TILES", "2")
     eng = Engine(0)
     try:
-        for seed, V, n_reads, k in ((1, 3, 700, 5), (2, 2, 300, 5), (3, 12, 2500, 3), (4, 40, 3000, 5), (5, 6, 300, 3)):
-            rng = np.random.default_rng(seed)
-            reads = [rng.integers(0, 2 * V, int(rng.integers(1, 15))) for _ in range(n_reads)]
-            for _ in range(n_reads // 10):  # a b a b ... with strands of their own, forwards or reverse-complemented
-                a, b = rng.integers(0, 2 * V, 2)
-                r = np.where(np.arange(int(rng.integers(k + 2, k + 6))) % 2 == 0, a, b)
-                reads.append(r if rng.random() < 0.5 else 2 * V - 1 - r[::-1])
-            order = rng.permutation(len(reads))
-            reads = [reads[i] for i in order]
-            toks = np.concatenate(reads).astype(np.int32)
-            offs = np.zeros(len(reads) + 1, np.int64)
-            np.cumsum([len(r) for r in reads], out=offs[1:])
+        for seed, V, n_reads, k in EDGE_CLASS_CASES:
+            toks, offs = edge_class_reads(seed, V, n_reads, k)  # random reads and planted a b a b ... reads
             eng.set_reads(toks, offs, 2 * V)
             eng.build(k)
             want = token_oracle.build(toks, offs, k, 2 * V)
@@ -365,7 +356,8 @@ SEAM_ARMS = [  # (environment, [(k, V, exact_keys as amg_counts reports it)])
                (11, 400, 2))     # 110 bits: fingerprint keys, the kernel with k at run time
 ] + [({"AMG_X_GENERIC_K": "1"}, [(3, 12, 1), (5, 30000, 1)]),   # exact keys through the kernel with k at run time
      ({"AMG_EDGE_HOME": "0"}, [(3, 12, 1), (5, 30000, 1)]),     # four consecutive adjacencies per thread
-     ({"AMG_CLAIM_SHARDS": "1", "AMG_X_HEAD_TILES": "1"}, [(3, 12, 1), (5, 30000, 1)])]  # a head tile, a dense tile, a shard's
+     ({"AMG_CLAIM_SHARDS": "1", "AMG_X_HEAD_TILES": "1"}, [(3, 12, 1), (5, 30000, 1)]),  # a head tile, a dense tile, a shard's
+     ({"AMG_KEY_MODE": "fp"}, [(3, 12, 0), (5, 30000, 0), (11, 400, 0)])]                # the 32-byte fingerprint path
 
 
 @pytest.mark.parametrize("env,shapes", SEAM_ARMS, ids=lambda a: "-".join(f"{k[4:]}={v}" for k, v in a.items())
@@ -374,7 +366,8 @@ def test_tile_seams_and_staging_routes(env, shapes, monkeypatch):
     """What the node and edge kernels do around a tile: reads that end one token before, at and one token after a tile
     seam, reads that lie across a seam with more than k genes on either side, and streams whose length is 0, 1, 2 and
     3 modulo the four results a thread stores at once — for one- and two-word keys in both packings, fingerprint keys,
-    k at compile and at run time, with and without minimiser buckets, home slots and shard counters.  At k = 3 and 5
+    k at compile and at run time, with and without minimiser buckets, home slots and shard counters, and on the 32-byte
+    fingerprint path (AMG_KEY_MODE=fp: stage_tile, k_node_upsert, k_edges).  At k = 3 and 5
     every stream is also built from a BORROWED device array that starts 4, 8 or 12 bytes after a 16-byte boundary (the
     tile then arrives by the scalar route instead of one 128-bit load per thread).  Everything against the sequential C
     oracle, exactly."""
