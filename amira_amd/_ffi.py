@@ -157,6 +157,12 @@ def _load():
         "amg_count_probe": (C.c_int, [P, C.c_int, C.c_int, P, I64, I64, P, I64, C.c_int, C.c_int, P, P]),
         "amg_nw_probe": (C.c_int, [P, I64, P, P, P, P, P, P, P, P, C.c_int, P, P, P, P]),
         "amg_correct_routes": (C.c_int, [P, P, I32]),
+        "amg_names_create": (C.c_int, [I32, P, I64, I32, C.POINTER(P)]),
+        "amg_names_destroy": (C.c_int, [P]),
+        "amg_node_names": (C.c_int, [P, P, P, I64, P, P]),
+        "amg_edge_names": (C.c_int, [P, P, P, I64, P, P]),
+        "amg_names_probe": (C.c_int, [P, P, P, I64, I32, I64, P, P]),
+        "amg_names_host": (C.c_int, [P, I64, I32, P, I64, I32, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here == header / library mismatch

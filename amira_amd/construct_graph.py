@@ -42,7 +42,8 @@ from .construct_edge import Edge
 from .construct_read import Read  # noqa: F401  (re-exported like the reference)
 from .engine import Engine, _ENGINE_POOL, acquire_engine as _acquire_engine, release_engine as _release_engine  # noqa: F401
 from .graph_paths import PathsAndOutput
-from .graph_view import _GraphNode, _LazyHashes, _RowIndex, _View, node_hash_of_tokens  # noqa: F401
+from .graph_view import (NamedSource, _GraphNode, _LazyHashes, _RowIndex, _View, hashes_of_token_rows,  # noqa: F401
+                         node_hash_of_tokens)
 from .io import TokenizedPositions, TokenizedReads
 from .read_clustering import ReadClustering
 from .read_correction import ReadCorrection
@@ -148,6 +149,7 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
         self._minEdgeCoverage = 1
         self._genePositions = gene_positions
         self._view = None
+        self._names_taken = 0      # names taken from the device by views dropped since and outside views (names_from_device)
         self._host_edits = False   # add_node / add_edge / remove_edge ... changed the host view
         self._lone_edges = set()   # directed edges removed one at a time (remove_edge) on the device
         self._known_rows = {}      # read name -> row for the reads the native clustering has looked at
@@ -306,7 +308,39 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
 
     # ------------------------------------------------------------------ view plumbing
     def _invalidate(self):
+        if self._view is not None:
+            self._names_taken += self._view.names_from_device
         self._view = None
+
+    @property
+    def names_from_device(self):
+        """node and edge names this graph took from the device in bulk so far (the others were hashed on the host)"""
+        return self._names_taken + (self._view.names_from_device if self._view is not None else 0)
+
+    def _names_source(self):
+        """the engine with the vocabulary's gene table bound to its naming calls (what views name batches with), or the
+        bare engine where the device's names cannot be relied on: an interpreter whose pickle or hash() differ from the
+        restated recipe (amira_amd.names.names_ok), a vocabulary without genes"""
+        from .names import names_ok
+        make = getattr(self._vocab, "gene_names", None)
+        names = make(self._engine.device) if make is not None and names_ok() else None
+        return self._engine if names is None else NamedSource(self._engine, names)
+
+    def _row_namer(self):
+        """rows of tokens -> (digests, py_hash) in one device call, for hashes that are made without a view; answers
+        None once the graph is closed (the caller then hashes on the host), None itself under AMG_NAMES_ON_HOST=1"""
+        if os.environ.get("AMG_NAMES_ON_HOST") == "1":
+            return None
+
+        def namer(rows):
+            if getattr(self, "_engine", None) is None:
+                return None
+            source = self._names_source()
+            if not isinstance(source, NamedSource):
+                return None
+            self._names_taken += len(rows)
+            return source.row_names(rows)
+        return namer
 
     def _settle_leases(self):
         """What an earlier correct_reads of this graph left on the device (amira_amd.io.DeviceCorrected: the lazy
@@ -341,7 +375,7 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
     def _v(self):
         if self._view is None:
             gs = self._gs
-            self._view = _View(self._engine, self._vocab, self._kmerSize, self._read_ids, self._read_off,
+            self._view = _View(self._names_source(), self._vocab, self._kmerSize, self._read_ids, self._read_off,
                                None if gs is None else (gs, self._ge), self._known_rows, self._row_index(),
                                self._gene_cache)
         return self._view
@@ -720,13 +754,14 @@ class GeneMerGraph(BubblePopping, ReadCorrection, PathsAndOutput, ReadClustering
         tokens = None if v is not None else self._engine.nodes()["tokens"]
         removed = self._run_pass("remove_short_linear_paths", int(min_length), protect)
         if v is not None:
+            v.ensure_hashes(removed.tolist(), removed_since=True)   # (a batch: one device call over the view's rows)
             hashes = [v.hash_at(i) for i in removed.tolist()]
         elif _lazy_hashes:
             # (the drivers, which ignore the result): the hashes — a sha256 per removed node, tens of thousands of
-            # them in a first sweep — are made when somebody looks at them
-            hashes = _LazyHashes(tokens[removed], self._vocab)
+            # them in a first sweep — are made when somebody looks at them, a batch of them in one device call
+            hashes = _LazyHashes(tokens[removed], self._vocab, self._row_namer())
         else:
-            hashes = [self._hash_of_tokens(tokens[i].tolist()) for i in removed.tolist()]
+            hashes = hashes_of_token_rows(self._vocab, tokens[removed], self._row_namer())
         if len(hashes):
             self._invalidate()
         return hashes

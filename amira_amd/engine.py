@@ -323,6 +323,38 @@ class Engine:
                                     _ffi.ptr(gs), _ffi.ptr(ge), _ffi.ptr(route), _ffi.ptr(state)))
         return gs[:total], ge[:total], route[:n], state
 
+    # ---- the 256-bit names of nodes and edges (include/amg.h, amg_node_names / amg_edge_names / amg_names_probe)
+    def _names_of(self, call, names, ids, total):
+        if ids is None:
+            n, p = total, None
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            n, p = len(ids), (ptr(ids) if len(ids) else None)
+        digests, py_hash = np.zeros((n, 32), np.uint8), np.zeros(n, np.int64)
+        check(call(self._h, names._h, p, n, ptr(digests) if n else None, ptr(py_hash) if n else None))
+        return digests, py_hash
+
+    def node_names(self, names, ids=None):
+        """(uint8 [n, 32], int64 [n]): the sha256 names of the nodes `ids` (any order, repeats allowed; None: all of
+        them) as big-endian bytes, and Python's hash() of each; a node that is not alive gets zeros.  names: the
+        GeneNames of the reads' vocabulary on this engine's device."""
+        return self._names_of(_ffi.lib.amg_node_names, names, ids, self.graph_sizes()[0] if ids is None else 0)
+
+    def edge_names(self, names, ids=None):
+        """the same for edges: Edge.__hash__ of every edge asked for, zeros for an edge that is not alive"""
+        return self._names_of(_ffi.lib.amg_edge_names, names, ids, self.graph_sizes()[1] if ids is None else 0)
+
+    def names_probe(self, names, rows, chunk_names=0):
+        """the names of arbitrary rows of tokens (an int array [n, k]) through the launcher and kernel of node_names,
+        chunk_names names per chunk (<= 0: the default); the engine need not hold a graph"""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        assert rows.ndim == 2
+        n, k = rows.shape
+        digests, py_hash = np.zeros((n, 32), np.uint8), np.zeros(n, np.int64)
+        check(_ffi.lib.amg_names_probe(self._h, names._h, ptr(rows) if n else None, n, k, int(chunk_names),
+                                       ptr(digests) if n else None, ptr(py_hash) if n else None))
+        return digests, py_hash
+
     def corrected(self, n_reads, n_tokens, with_positions, buf=None, pos32=False):
         """the corrected set on the host.  pos32: the positions as int32 arrays (gathered on the device, half the bytes
         over PCIe) when every one of them fits — int64 otherwise, as without the flag"""
@@ -687,6 +719,34 @@ class Sequences:
     def close(self):
         if getattr(self, "_h", None):
             _ffi.lib.amg_seqs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class GeneNames:
+    """the gene table of a vocabulary resident on a device (amg_names_create): what Engine.node_names / edge_names /
+    names_probe name rows of tokens with.  gene_digests: uint8 [n_genes, 32], the sha256 of every gene name in rank
+    order.  One handle serves every engine of that vocabulary on the device."""
+
+    def __init__(self, gene_digests, device=0, pickle_protocol=None):
+        import pickle
+        self._h = None
+        digests = np.ascontiguousarray(gene_digests, dtype=np.uint8).reshape(-1, 32)
+        self.device, self.n_genes = int(device), len(digests)
+        self.pickle_protocol = pickle.DEFAULT_PROTOCOL if pickle_protocol is None else int(pickle_protocol)
+        h = C.c_void_p()
+        check(_ffi.lib.amg_names_create(self.device, ptr(digests) if len(digests) else None, len(digests),
+                                        self.pickle_protocol, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _ffi.lib.amg_names_destroy(self._h)
             self._h = None
 
     def __del__(self):

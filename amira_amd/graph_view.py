@@ -4,6 +4,7 @@ and per-read lists, made lazily from the device's integer arrays (DESIGN.md "Dat
 A _View is built from an ARRAY SOURCE — anything with nodes(), edges(), node_adj(), read_node_ids(), read_dirs(),
 node_reads() and read_node_ids_of(); in production the Engine — and from plain facts about the reads.  It never sees
 the GeneMerGraph that owns it, so it cannot keep that graph alive, and it can be built without a device."""
+import os
 from collections.abc import Mapping, Sequence
 
 import numpy as np
@@ -20,6 +21,52 @@ def node_hash_of_tokens(vocab, toks):
     signed gene hashes"""
     signed = vocab.signed_hash
     return hashlib_hash(tuple([signed(t) for t in toks]))
+
+
+# Where naming on the device overtakes the host recipe (tools/names_probe.py, profiles/names_host_vs_device.json; DESIGN.md
+# section 4): a batch of at least NAMES_BATCH_MIN unnamed nodes or edges is named in one device call, smaller asks keep
+# the host recipe; once a view has named more than NAMES_ONE_BY_ONE of them one by one, the next ask names every live one
+# still unnamed in one call (the policy window_ids has for rows).  Measured on an MI355X: a call for 64 ids costs 83 us
+# (nodes) / 105 us (edges) against 103 / 100 us of hashing them on the host, for 128 ids 88 / 110 us against 209 / 204 us,
+# and the device stays below from there on; 128 is the first power of two at which it is below for both kinds.
+NAMES_BATCH_MIN = 128
+NAMES_ONE_BY_ONE = 128
+
+
+def ints_of_digests(digests):
+    """the rows of a uint8 [n, 32] array as Python ints (big-endian)"""
+    raw, from_bytes = digests.tobytes(), int.from_bytes
+    return [from_bytes(raw[a:a + 32], "big") for a in range(0, len(raw), 32)]
+
+
+def hashes_of_token_rows(vocab, rows, row_names=None):
+    """node hashes of the rows of a token matrix: from NAMES_BATCH_MIN rows on in one device call when there is a namer
+    (row_names: rows -> (digests, py_hash), or None when it cannot serve), else one by one on the host"""
+    if row_names is not None and len(rows) >= NAMES_BATCH_MIN:
+        got = row_names(rows)
+        if got is not None:
+            return ints_of_digests(got[0])
+    return [node_hash_of_tokens(vocab, row) for row in rows.tolist()]
+
+
+class NamedSource:
+    """an array source (the Engine) with the gene table of one vocabulary bound to its naming calls: what a
+    GeneMerGraph hands its views, so that they can name nodes and edges in bulk"""
+
+    def __init__(self, engine, names):
+        self._engine, self._names = engine, names
+
+    def __getattr__(self, name):
+        return getattr(self._engine, name)
+
+    def node_names(self, ids):
+        return self._engine.node_names(self._names, ids)
+
+    def edge_names(self, ids):
+        return self._engine.edge_names(self._names, ids)
+
+    def row_names(self, rows):
+        return self._engine.names_probe(self._names, rows)
 
 
 def gene_obj(cache, vocab, token):
@@ -102,13 +149,13 @@ class _LazyReadLists(Mapping):
 class _LazyHashes(Sequence):
     """node hashes of the rows of a token matrix, computed on first use (a list from then on)"""
 
-    def __init__(self, token_rows, vocab):
-        self._rows, self._vocab, self._made = token_rows, vocab, None
+    def __init__(self, token_rows, vocab, row_names=None):
+        self._rows, self._vocab, self._made, self._row_names = token_rows, vocab, None, row_names
 
     def _list(self):
         if self._made is None:
-            self._made = [node_hash_of_tokens(self._vocab, row) for row in self._rows.tolist()]
-            self._rows = None
+            self._made = hashes_of_token_rows(self._vocab, self._rows, self._row_names)
+            self._rows = self._row_names = None
         return self._made
 
     def __len__(self):
@@ -235,7 +282,8 @@ class _View:
     __slots__ = ("_nodes", "_nodes_complete", "_node_obj", "_id_of", "node_of_hash", "_edges", "_edges_complete",
                  "_edge_obj", "_n_edges", "readNodes", "readNodeDirections", "readNodePositions", "node_hash",
                  "edge_hash", "alive", "arrays", "_nh_table", "_vocab", "_k", "_read_ids", "_read_off", "_positions",
-                 "_known_rows", "_row_index", "_gene_cache", "_single_rows")
+                 "_known_rows", "_row_index", "_gene_cache", "_single_rows", "_names_source", "names_from_device",
+                 "_one_by_one", "_edge_id_of", "_py_hash", "_py_known")
 
     def __init__(self, source, vocab, k, read_ids, read_off, positions, known_rows, row_index, gene_cache):
         """positions: the flat (gene starts, gene ends) aligned with the tokens, or None; known_rows / row_index: the
@@ -253,6 +301,15 @@ class _View:
         self.edge_hash, self._edge_obj = [None] * E, [None] * E
         self._edges, self._edges_complete, self._n_edges = {}, False, E
         self._single_rows = 0
+        # naming in bulk: a source that offers node_names(ids) / edge_names(ids) -> (digests uint8 [n, 32], py_hash int64
+        # [n]) names batches (NAMES_BATCH_MIN); one without them, or AMG_NAMES_ON_HOST=1 when the view is made, keeps
+        # the host recipe for every name
+        named = hasattr(source, "node_names") and hasattr(source, "edge_names")
+        self._names_source = source if named and os.environ.get("AMG_NAMES_ON_HOST") != "1" else None
+        self.names_from_device = 0       # names (nodes and edges) this view took from the device
+        self._one_by_one = [0, 0]        # nodes, edges named on the host so far
+        self._edge_id_of = {}            # edge hash -> device edge id, of the edges hashed so far
+        self._py_hash, self._py_known = None, None   # hash() of the node hashes by device id (py_hash_of)
         self.readNodes = _LazyReadLists(self, self._read_nodes)
         self.readNodeDirections = _LazyReadLists(self, self._read_dirs)
         self.readNodePositions = _LazyReadLists(self, self._read_positions)
@@ -261,7 +318,7 @@ class _View:
         """called when the graph is closed: let go of the array source and cut the view's reference cycles (its lists
         and nodes point back at it) so that it is freed the moment its graph lets go of it, not when the cyclic
         collector next walks the heap"""
-        self.arrays.source = self.node_of_hash = None
+        self.arrays.source = self.node_of_hash = self._names_source = None
         self.readNodes = self.readNodeDirections = self.readNodePositions = None
         for node in self._nodes.values():   # (the nodes made so far)
             if isinstance(node, _GraphNode):
@@ -278,11 +335,53 @@ class _View:
             self._nh_table[i] = h
 
     def _hash_node(self, i):
+        """the host recipe for one node"""
         if not self.alive[i]:
             return None
         h = node_hash_of_tokens(self._vocab, self.arrays["nodes"]["tokens"][i].tolist())
         self._note_hash(i, h)
         return h
+
+    def _names_from_device(self, ids, by_rows):
+        """the names of the live nodes `ids` in one device call, as ints, or None when the device does not hold the
+        graph this view was made of any more (a live node came back without a name).  by_rows: from the view's own
+        token rows (ids the device may have removed since)"""
+        src = self._names_source
+        if by_rows:
+            digests, py = src.row_names(self.arrays["nodes"]["tokens"][ids])
+        else:
+            digests, py = src.node_names(np.asarray(ids, np.int32))
+        if len(ids) and not digests.any(axis=1).all():
+            return None
+        if self._py_hash is None:
+            self._py_hash, self._py_known = np.zeros(len(self.node_hash), np.int64), np.zeros(len(self.node_hash), bool)
+        self._py_hash[ids], self._py_known[ids] = py, True
+        self.names_from_device += len(ids)
+        return ints_of_digests(digests)
+
+    def _name_batch(self, kind, todo, host_one, device_many, all_unnamed):
+        """the policy of both kinds of names (kind 0: nodes, 1: edges) for `todo`, distinct live ids without a name:
+        one device call from NAMES_BATCH_MIN on, the host recipe below — until the view has named more than
+        NAMES_ONE_BY_ONE that way, when every live id still unnamed is named in one call"""
+        if not todo:
+            return
+        if self._names_source is not None:
+            if len(todo) < NAMES_BATCH_MIN and self._one_by_one[kind] > NAMES_ONE_BY_ONE and all_unnamed is not None:
+                todo = all_unnamed()
+            if (len(todo) >= NAMES_BATCH_MIN or self._one_by_one[kind] > NAMES_ONE_BY_ONE) and device_many(todo):
+                return
+        self._one_by_one[kind] += len(todo)
+        for i in todo:
+            host_one(i)
+
+    def _device_nodes(self, todo, by_rows=False):
+        got = self._names_from_device(todo, by_rows)
+        if got is None:
+            return False
+        note = self._note_hash
+        for i, h in zip(todo, got):
+            note(i, h)
+        return True
 
     def _make_node(self, i):
         if not self.alive[i]:
@@ -293,7 +392,8 @@ class _View:
         rc = [gene_obj(cache, vocab, flip(t)) for t in reversed(toks)]
         h = self.node_hash[i]
         if h is None:
-            h = node_hash_of_tokens(vocab, toks)
+            self._name_nodes((i,))
+            h = self.node_hash[i]
         node = _GraphNode(GeneMer._from_parts(canon, rc, int(nodes["first_dir"][i]), h))
         node.nodeCoverage = int(nodes["coverage"][i])
         node._component_ID = int(nodes["component"][i])
@@ -313,7 +413,10 @@ class _View:
     def _edge_list(self, lo, hi):
         """hashes of the live edges among adj_edge[lo:hi]: a node's forward list, or its backward list"""
         alive = self.arrays["edges"]["alive"]
-        return [self.edge_hash_of(e) for e in self.arrays["adj_edge"][lo:hi].tolist() if alive[e]]
+        live = [e for e in self.arrays["adj_edge"][lo:hi].tolist() if alive[e]]
+        self.ensure_edge_hashes(live)
+        eh = self.edge_hash
+        return [eh[e] for e in live]
 
     def node_at(self, i):
         """the node with device id i (None: removed)"""
@@ -325,23 +428,47 @@ class _View:
 
     def hash_at(self, i):
         h = self.node_hash[i]
-        if h is None and not self._nodes_complete:
-            h = self._hash_node(i)
+        if h is None and not self._nodes_complete and self.alive[i]:
+            self._name_nodes((i,))
+            h = self.node_hash[i]
         return h
 
-    def ensure_hashes(self, ids):
-        """node_hash[i] filled in for every id >= 0 of `ids` (an iterable of ints) — the hash alone (one sha256 of the
-        node's tokens); the Node object with its genes is made when somebody asks for the node itself"""
+    def _name_nodes(self, ids, removed_since=False):
+        nh, alive = self.node_hash, self.alive
+        todo = list(dict.fromkeys(i for i in ids if i >= 0 and nh[i] is None and alive[i]))
+        if removed_since:
+            self._name_batch(0, todo, self._hash_node, lambda t: self._device_nodes(t, True), None)
+        else:
+            self._name_batch(0, todo, self._hash_node, self._device_nodes,
+                             lambda: [i for i in np.flatnonzero(alive).tolist() if nh[i] is None])
+
+    def ensure_hashes(self, ids, removed_since=False):
+        """node_hash[i] filled in for every id >= 0 of `ids` (an iterable of ints) — the hash alone; the Node object
+        with its genes is made when somebody asks for the node itself.  A batch of NAMES_BATCH_MIN ids or more is
+        named in one device call where the source offers one (_name_batch).  removed_since: the device may have
+        removed nodes of `ids` since the view was made (tip clipping's answer): they are named from the view's rows"""
         if self._nodes_complete:
             return
-        nh, hash_node = self.node_hash, self._hash_node
-        for i in ids:
-            if i >= 0 and nh[i] is None:
-                hash_node(i)
+        self._name_nodes(ids, removed_since)
+
+    def py_hash_of(self, ids):
+        """int64 array: Python's hash() of the node hash of every id of `ids` (live nodes), without making the big
+        ints where the names come from the device"""
+        ids = np.asarray(ids, np.int64)
+        self.ensure_hashes(np.unique(ids).tolist())
+        if self._py_hash is None:
+            self._py_hash, self._py_known = np.zeros(len(self.node_hash), np.int64), np.zeros(len(self.node_hash), bool)
+        new = np.unique(ids[~self._py_known[ids]])
+        if len(new):
+            nh = self.node_hash
+            self._py_hash[new] = [hash(nh[i]) for i in new.tolist()]
+            self._py_known[new] = True
+        return self._py_hash[ids]
 
     @property
     def nodes(self):
         if not self._nodes_complete:
+            self._name_nodes(range(len(self.node_hash)))
             ordered = {}
             for i in range(len(self.node_hash)):
                 node = self.node_at(i)
@@ -380,29 +507,68 @@ class _View:
         edge._amg_id = e
         return edge
 
+    def _hash_edge(self, e):
+        """the host recipe for one edge: the Edge object of its two Node objects, and its __hash__"""
+        edge = self._edge_obj[e] = self._make_edge(e)
+        h = self.edge_hash[e] = edge.__hash__()
+        self._edges[h] = edge
+        self._edge_id_of[h] = e
+
+    def _device_edges(self, todo):
+        """edge_hash filled for the live edges `todo` from one device call: no Edge, no Node object is made for it"""
+        digests, _ = self._names_source.edge_names(np.asarray(todo, np.int32))
+        if not digests.any(axis=1).all():
+            return False   # (the device holds another graph by now: see _names_from_device)
+        eh, id_of = self.edge_hash, self._edge_id_of
+        for e, h in zip(todo, ints_of_digests(digests)):
+            eh[e] = h
+            id_of[h] = e
+        self.names_from_device += len(todo)
+        return True
+
+    def ensure_edge_hashes(self, ids):
+        """edge_hash[e] filled in for every LIVE edge of `ids`: in one device call for NAMES_BATCH_MIN edges or more
+        where the source offers one (_name_batch), else edge by edge from the objects"""
+        eh, alive = self.edge_hash, self.arrays["edges"]["alive"]
+        todo = list(dict.fromkeys(e for e in ids if eh[e] is None and alive[e]))
+        self._name_batch(1, todo, self._hash_edge, self._device_edges,
+                         lambda: [e for e in np.flatnonzero(alive).tolist() if eh[e] is None])
+
     def edge_hash_of(self, e):
         h = self.edge_hash[e]
         if h is None:
-            edge = self._edge_obj[e] = self._make_edge(e)
-            h = self.edge_hash[e] = edge.__hash__()
-            self._edges[h] = edge
+            self.ensure_edge_hashes((e,))
+            h = self.edge_hash[e]
         return h
+
+    def _edge_at(self, e):
+        """the Edge object of the live, hashed edge e (made on first use)"""
+        edge = self._edge_obj[e]
+        if edge is None:
+            edge = self._edge_obj[e] = self._make_edge(e)
+            self._edges.setdefault(self.edge_hash[e], edge)
+        return edge
 
     @property
     def edges(self):
         if not self._edges_complete:
             alive = self.arrays["edges"]["alive"]
-            ordered = {}
-            for e in range(self._n_edges):
-                if alive[e]:
-                    h = self.edge_hash_of(e)
-                    ordered[h] = self._edge_obj[e]
+            live = np.flatnonzero(alive).tolist()
+            self.ensure_edge_hashes(live)
+            ends = self.arrays["edges"]
+            self._name_nodes(np.unique(np.concatenate([ends["src"][live], ends["tgt"][live]])).tolist())  # (the objects' nodes)
+            eh, ordered = self.edge_hash, {}
+            for e in live:
+                ordered[eh[e]] = self._edge_at(e)
             self._edges, self._edges_complete = ordered, True
         return self._edges
 
     def edge_by_hash(self, h):
         got = self._edges.get(h)
-        return got if got is not None else self.edges[h]
+        if got is None:
+            e = self._edge_id_of.get(h)   # hashed already (on the device: no object yet)
+            got = self._edge_at(e) if e is not None else self.edges[h]
+        return got
 
     # ---- per-read lists (the makers of readNodes, readNodeDirections, readNodePositions; r is a read's row)
     def window_ids(self, r):

@@ -584,7 +584,7 @@ class ReadClustering:
             py_hash, known = memo[1], memo[2]
             new = uniq[~known[uniq]]
             if len(new):
-                py_hash[new] = [hash(h) for h in nh[new].tolist()]
+                py_hash[new] = v.py_hash_of(new)   # (as the device made them with the names, where it made the names)
                 known[new] = True
             anchor_list = list(anchors)                   # the set's iteration order, as `for a1 in nodeAnchors` meets it
             by_hash = {h: i for i, h in enumerate(sorted(anchor_list))}

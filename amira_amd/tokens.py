@@ -55,6 +55,7 @@ class Vocabulary:
         self = cls.__new__(cls)
         self.names = list(names)
         self.hashes = [int.from_bytes(bytes(d), "big") for d in digests]
+        self._digests = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)   # (kept as the loader gave them)
         self.rank = {n: i for i, n in enumerate(self.names)}
         self.V = len(self.names)
         self.two_v = 2 * max(self.V, 1)
@@ -81,6 +82,37 @@ class Vocabulary:
     def signed_hash(self, token):
         V = max(self.V, 1)
         return self.hashes[token - V] if token >= V else -self.hashes[V - 1 - token]
+
+    def digest_bytes(self):
+        """uint8 [V, 32]: the genes' sha256 digests in rank order, big-endian (what amg_names_create takes)"""
+        d = getattr(self, "_digests", None)
+        if d is None:
+            raw = b"".join(h.to_bytes(32, "big") for h in self.hashes)
+            d = self._digests = np.frombuffer(raw, np.uint8).reshape(len(self.hashes), 32).copy()
+        return d
+
+    def gene_names(self, device=0):
+        """the vocabulary's gene table on `device` (amira_amd.engine.GeneNames), made on first use, one per device,
+        shared by every graph of the vocabulary and released with it; None for a vocabulary without genes"""
+        if self.V < 1:
+            return None
+        made = self.__dict__.setdefault("_gene_names", {})
+        got = made.get(int(device))
+        if got is None:
+            from .engine import GeneNames
+            got = made[int(device)] = GeneNames(self.digest_bytes(), int(device))
+        return got
+
+    def __del__(self):
+        for names in self.__dict__.get("_gene_names", {}).values():
+            try:
+                names.close()
+            except Exception:  # noqa: BLE001
+                pass
+
+    def __getstate__(self):
+        # (device handles stay behind: a copy or an unpickled vocabulary makes its own on first use)
+        return {k: v for k, v in self.__dict__.items() if k != "_gene_names"}
 
     def strand(self, token):
         return 1 if token >= max(self.V, 1) else -1

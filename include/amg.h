@@ -555,6 +555,39 @@ int64_t amg_py_tuple_hash(const int64_t* item_hashes, int64_t n);
 int amg_pyset_script(const int32_t* ops, int64_t n_ops, const int64_t* key_hash, int32_t n_sets,
                      int32_t* out_keys, int64_t* out_off);
 
+/* ---- the 256-bit names of nodes and edges (construct_gene_mer.py:94-97, construct_edge.py:104-124) made on the device.
+ *      A node's name is SHA-256 of pickle.dumps(tuple of its k signed gene hashes), read as a big-endian unsigned
+ *      integer; an edge's name is the smaller of the names of (s, t) and (-s, -t), s = name(source) * sdir, t =
+ *      name(target) * tdir.  pickle's bytes for protocols 4 and 5 are restated (amira_amd/csrc/amg_names.h states the
+ *      rule once for the kernel and the host twin); py_hash is Python's hash() of the name, name mod 2^61 - 1.
+ *      amg_names_create: the gene table on a device — gene_digests[n_genes][32], the sha256 of every gene name in RANK
+ *      order (HOST memory, copied during the call).  One handle serves every ctx of that vocabulary on the device.
+ *      n_genes < 1 or a protocol other than 4 / 5: AMG_E_ARG.
+ *      amg_node_names / amg_edge_names: readers of a built graph (a rank of a merged graph included) that change
+ *      nothing of it; their scratch is released inside the call.  ids: n node / edge ids in any order, repeats allowed
+ *      (HOST), or NULL for all of them, 0 .. n - 1 (n must then be the graph's number).  digests[n][32] big-endian;
+ *      py_hash[n] or NULL.  An id whose node / edge is not alive gets 32 zero bytes and py_hash 0.  AMG_E_ARG before any
+ *      launch: 2 n_genes differs from the ctx's two_v, an id outside the graph, handle and ctx on different devices.
+ *      Output passes through a bounded device buffer (2^22 names) that is copied out chunk by chunk.
+ *      amg_names_probe (tests): arbitrary rows[n][k] of tokens (HOST) through the same launcher and kernel, chunk_names
+ *      names per chunk (<= 0: the default); the ctx need not hold a graph.  A token outside [0, 2 n_genes) or k outside
+ *      [1, 256]: AMG_E_ARG.
+ *      amg_names_host: the same rows by the host twin built from the same header; no device call, no ctx.  It is what
+ *      the rule is tested with where there is no GPU and what the Python layer holds against the running interpreter;
+ *      nothing in the product routes work to it. ---------------------------------------------------------------- */
+typedef struct amg_names amg_names;
+int amg_names_create(int32_t device, const uint8_t* gene_digests, int64_t n_genes, int32_t pickle_protocol,
+                     amg_names** out);
+int amg_names_destroy(amg_names* names);
+int amg_node_names(amg_ctx* ctx, const amg_names* names, const int32_t* node_ids, int64_t n, uint8_t* digests,
+                   int64_t* py_hash);
+int amg_edge_names(amg_ctx* ctx, const amg_names* names, const int32_t* edge_ids, int64_t n, uint8_t* digests,
+                   int64_t* py_hash);
+int amg_names_probe(amg_ctx* ctx, const amg_names* names, const int32_t* rows, int64_t n, int32_t k,
+                    int64_t chunk_names, uint8_t* digests, int64_t* py_hash);
+int amg_names_host(const uint8_t* gene_digests, int64_t n_genes, int32_t pickle_protocol, const int32_t* rows, int64_t n,
+                   int32_t k, uint8_t* digests, int64_t* py_hash);
+
 /* ---- per-stage device time of the last call, for bench.py ------------------------- */
 /* names[i] points at static strings; returns the number of stages (<= cap). */
 int amg_last_timings(amg_ctx* ctx, const char** names, float* ms, int cap);
