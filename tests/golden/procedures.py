@@ -7,6 +7,7 @@ the real reference (gen_goldens.py, build container only), the CPU oracle
 """
 import importlib.util
 import os
+from collections import Counter
 
 import dump as D
 
@@ -244,7 +245,10 @@ def _label_path(g, hashes):
     return [g.get_gene_mer_label(g.get_node_by_hash(h)) for h in hashes]
 
 
-def _bubble_entry(g, fq, genes_of_interest):
+def _bubble_entry(g, fq, genes_of_interest, facts=None):
+    """facts: a dict that takes what the entry does not say (reads and genes before the step, reads whose genes the
+    step changed) — for the non-vacuity checks below, never part of the entry"""
+    before = {r: list(v) for r, v in g.get_reads().items()} if facts is not None else None
     starts = g.identify_potential_bubble_starts()
     entry = {"starts": {str(c): [[g.get_gene_mer_label(g.get_node_by_hash(h)), d] for h, d in v]
                         for c, v in starts.items()}}
@@ -263,7 +267,48 @@ def _bubble_entry(g, fq, genes_of_interest):
     entry["reads_digest"] = D.digest({r: list(v) for r, v in reads.items()})
     entry["positions_digest"] = D.digest({r: [list(p) for p in v] for r, v in pos.items()})
     entry["n_genes"] = sum(len(v) for v in reads.values())
+    if facts is not None:
+        facts["n_reads"] = len(before)
+        facts["n_genes_before"] = sum(len(v) for v in before.values())
+        facts["reads_changed"] = sum(1 for r, v in before.items() if list(reads[r]) != v)
     return entry
+
+
+def bubble_case_facts(entry, facts=None):
+    """what makes a bubble entry worth having, read from the entry (and from `facts` where given): start components,
+    the most paths between one pair of terminals, the nodes of the longest path, path coverages, reads rewritten"""
+    n_between, longest = Counter(), 0
+    for component in entry["paths"]:
+        for labels, _coverage in component["filtered"]:
+            n_between[(component["component"],) + tuple(sorted([str(labels[0]), str(labels[-1])]))] += 1
+            longest = max(longest, len(labels))
+    out = {"start_components": len(entry["starts"]), "junctions": sum(len(v) for v in entry["starts"].values()),
+           "paths": sum(n_between.values()), "most_paths_between_terminals": max(n_between.values(), default=0),
+           "longest_path": longest, "path_coverages": len(entry["path_coverages"])}
+    out.update(facts or {})
+    return out
+
+
+def assert_bubble_case_not_vacuous(name, entry, facts, long_path=False):
+    """the rules for a bubble case: a start component, two ways between some pair of terminals, two path coverages, a
+    read whose genes the step changed — and, where `long_path`, a path of more than 2k nodes, which only a search as
+    deep as 4k finds"""
+    f = bubble_case_facts(entry, facts)
+    k = CASES[name][1][4]
+    assert f["start_components"] >= 1 and f["most_paths_between_terminals"] >= 2 and f["path_coverages"] >= 2, (name, f)
+    assert f["reads_changed"] >= 1, (name, f)
+    assert not long_path or f["longest_path"] > 2 * k, (name, f)
+    return f
+
+
+def assert_sweep_case_not_vacuous(name, entry):
+    assert entry["n_removed"] > 0, (name, entry["n_removed"])
+    assert entry["corrected1"]["n_reads"] < entry["N"], (name, entry["corrected1"]["n_reads"], entry["N"])
+
+
+def assert_planted_case_not_vacuous(name, entry):
+    per_gene = Counter(row[1] for row in entry["allele_sizes"])
+    assert max(per_gene.values(), default=0) > 1, (name, dict(per_gene))
 
 
 def p_bubbles_real(impl):
@@ -288,7 +333,7 @@ def p_bubbles_synth(impl, name, k, min_cov):
     return _bubble_entry(g, fq, set())
 
 
-def p_bubbles_random(impl, seed, N, L, V, k, err, min_cov=3):
+def p_bubbles_random(impl, seed, N, L, V, k, err, min_cov=3, facts=None):
     """bubble popping (correct_low_coverage_paths with its MinHash containment test) on random reads with compact
     gene positions (60-base genes every 80 bases: nucleotide reads of a few kilobases, so that the pure-Python
     sketch of the oracle stays fast) after filter + correction, as the cleaning loop runs it — for the
@@ -301,7 +346,7 @@ def p_bubbles_random(impl, seed, N, L, V, k, err, min_cov=3):
     g.filter_graph(min_cov, 1)
     calls, pos = g.correct_reads(fq)
     g = impl.GeneMerGraph(calls, k, pos)
-    return _bubble_entry(g, fq, set())
+    return _bubble_entry(g, fq, set(), facts)
 
 
 def p_iterative(impl, which):
@@ -321,6 +366,26 @@ def p_iterative(impl, which):
         reads, positions = impl.iterative_bubble_popping(calls, pos, 3, k, 1, short, short_pos, fq, tmp,
                                                          min_cov, set(), 2)
     return {"n_reads": len(reads), "n_genes": sum(len(v) for v in reads.values()),
+            "reads_digest": D.digest({r: list(v) for r, v in reads.items()}),
+            "positions_digest": D.digest({r: [list(p) for p in v] for r, v in positions.items()}),
+            "short_reads": sorted(short)}
+
+
+def p_iterative_synth(impl, seed, N, L, V, k, err, min_cov=3):
+    """iterative_bubble_popping at a gene-mer size of one's choice: random reads with compact gene positions and the
+    nucleotide reads that go with them, as p_bubbles_random makes them"""
+    import tempfile
+    ids, sts = synth.loop_reads(seed, N, L, V, err, 0)
+    calls = synth.to_read_dict(ids, sts, synth.gene_names(V, 0))
+    pos = {r: [(80 * i, 80 * i + 59) for i in range(len(g))] for r, g in calls.items()}
+    fq = synth_fastq(calls, pos, flank=40)
+    n_genes_in = sum(len(v) for v in calls.values())
+    short, short_pos = {}, {}
+    with tempfile.TemporaryDirectory() as tmp:
+        reads, positions = impl.iterative_bubble_popping(calls, pos, 3, k, 1, short, short_pos, fq, tmp,
+                                                         min_cov, set(), 2)
+    return {"n_reads_in": N, "n_genes_in": n_genes_in, "n_reads": len(reads),
+            "n_genes": sum(len(v) for v in reads.values()),
             "reads_digest": D.digest({r: list(v) for r, v in reads.items()}),
             "positions_digest": D.digest({r: [list(p) for p in v] for r, v in positions.items()}),
             "short_reads": sorted(short)}
@@ -520,3 +585,53 @@ CASES["read_helpers_four_k5"] = (p_read_helpers, ("four", 5), False)
 CASES["front_end_five"] = (p_front_end, ("five", False), False)
 CASES["front_end_nine"] = (p_front_end, ("nine", False), False)
 CASES["front_end_six_blanks"] = (p_front_end, ("six", True), False)
+# gene-mer sizes 7 ... 16 (choose_kmer_size picks up to 15, the native interface takes up to 16): reads of at least
+# 2k + 20 genes, a few hundred of them, so that the reference needs seconds.  Seeds and sizes are chosen so that no case
+# is vacuous ON THE REFERENCE (NOT_VACUOUS below; gen_goldens.py and tests/test_oracle_goldens.py assert it); none raises
+# the palindrome assertion of an even k
+CASES["bubbles_random_k7"] = (p_bubbles_random, (307, 120, 34, 150, 7, 0.03), False)
+CASES["bubbles_random_k9"] = (p_bubbles_random, (316, 120, 38, 150, 9, 0.03), False)
+CASES["bubbles_random_k11"] = (p_bubbles_random, (109, 150, 44, 100, 11, 0.04), False)
+CASES["bubbles_random_k15"] = (p_bubbles_random, (103, 120, 50, 120, 15, 0.03), False)
+CASES["bubbles_random_k16"] = (p_bubbles_random, (211, 120, 56, 80, 16, 0.04), False)
+CASES["planted_k9"] = (p_planted, (75, 200, 46, 600, 9), False)
+CASES["planted_k11"] = (p_planted, (79, 200, 50, 600, 11), False)
+CASES["planted_k15"] = (p_planted, (81, 200, 56, 600, 15), False)
+CASES["sweep_k9"] = (p_sweep, (158, 300, 40, 250, 9, 0.08), False)
+CASES["sweep_k11"] = (p_sweep, (162, 300, 44, 250, 11, 0.08), False)
+CASES["sweep_k13"] = (p_sweep, (164, 300, 48, 250, 13, 0.08), False)
+CASES["sweep_k15"] = (p_sweep, (166, 300, 52, 250, 15, 0.07), False)
+CASES["sweep_k16"] = (p_sweep, (173, 300, 58, 200, 16, 0.07), False)
+CASES["iterative_synth_k9"] = (p_iterative_synth, (101, 120, 36, 100, 9, 0.04), False)
+
+
+def _iterative_case_not_vacuous(name, entry):
+    assert entry["n_reads"] > 0 and entry["n_genes"] < entry["n_genes_in"], (name, entry["n_genes"], entry["n_genes_in"])
+
+
+# name -> check(name, entry[, facts]) of what makes the case worth having.  A bubble case's check wants the `facts` that
+# p_bubbles_random leaves behind; at k = 15 and 16 a path of more than 2k nodes, which a search of 4k levels admits
+NOT_VACUOUS = {}
+for _k in (7, 9, 11, 15, 16):
+    NOT_VACUOUS[f"bubbles_random_k{_k}"] = (
+        lambda name, entry, facts, _long=_k >= 15: assert_bubble_case_not_vacuous(name, entry, facts, _long))
+for _k in (9, 11, 13, 15, 16):
+    NOT_VACUOUS[f"sweep_k{_k}"] = assert_sweep_case_not_vacuous
+for _k in (9, 11, 15):
+    NOT_VACUOUS[f"planted_k{_k}"] = assert_planted_case_not_vacuous
+NOT_VACUOUS["iterative_synth_k9"] = _iterative_case_not_vacuous
+
+
+def run_case(impl, name):
+    """the entry of a case and, where the case has a non-vacuity check, that check's verdict on THIS implementation"""
+    proc, args, _ = CASES[name]
+    check = NOT_VACUOUS.get(name)
+    if proc is p_bubbles_random and check is not None:
+        facts = {}
+        entry = proc(impl, *args, facts=facts)
+        check(name, entry, facts)
+    else:
+        entry = proc(impl, *args)
+        if check is not None:
+            check(name, entry)
+    return entry

@@ -14,6 +14,11 @@ pytestmark = pytest.mark.gpu
 
 CASES = [(71, 300, 30, 120, 3, 0.04), (72, 400, 25, 90, 3, 0.05), (73, 300, 40, 150, 5, 0.04), (74, 200, 30, 60, 4, 0.05),
          (75, 500, 30, 200, 3, 0.03)]
+# k = 7, 9, 11, 15, 16: few junctions (the reference-shaped pair search is quadratic in them), none of them vacuous (the
+# rules of procedures.NOT_VACUOUS, checked below on the product's reference-shaped methods), no palindromic gene-mer
+LARGE_K = [P.CASES["bubbles_random_k%d" % k][1] for k in (7, 9, 11, 15, 16)]
+# k = 16, five junctions: 7 paths within 63 nodes, 9 within 64, two of them 64 nodes long
+AT_THE_LIMIT = (412, 120, 56, 80, 16, 0.04)
 
 
 def _graph(seed, N, L, V, k, err, min_cov=3):
@@ -31,9 +36,10 @@ def _graph(seed, N, L, V, k, err, min_cov=3):
         return None, None
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + LARGE_K)
 def test_paths_between_junctions_one_search_per_start(case):
     g, _ = _graph(*case)
+    assert g is not None or case not in LARGE_K
     if g is None:
         pytest.skip("palindromic gene-mer")
     found = g._junction_paths_on_device()
@@ -42,7 +48,7 @@ def test_paths_between_junctions_one_search_per_start(case):
     assert components == g.components()
     starts = g.identify_potential_bubble_starts()
     assert sorted(paths_of) == sorted(starts)
-    n_paths = 0
+    n_paths = longest = 0
     for component, junctions in starts.items():
         want = g.get_all_paths_between_junctions_in_component(junctions, g.get_kmerSize() * 4, 1)
         got = set()
@@ -51,7 +57,12 @@ def test_paths_between_junctions_one_search_per_start(case):
         # the same paths, put into the set in the same order
         assert list(got) == want
         n_paths += len(want)
+        longest = max([longest] + [len(p) for p in want])
     assert n_paths > 0 or not starts
+    if case in LARGE_K:
+        k = case[4]
+        assert starts and n_paths >= 2
+        assert k < 15 or longest > 2 * k   # (a path that only a search as deep as 4k admits)
 
 
 def _paths_per_start(g, distance):
@@ -73,12 +84,22 @@ def _paths_per_start(g, distance):
 def test_junction_search_prunes_at_every_distance():
     """the search's bound is the junction visitor's answer to the shared search loop, and bubble popping only ever asks
     for 4k: the paths per (start, stop) pair at distances 2, 3 and 4k against new_find_paths_between_nodes"""
-    g, _ = _graph(*CASES[0])
+    _search_prunes(CASES[0], 3)
+
+
+def test_junction_search_prunes_at_the_entry_points_limit():
+    """the same at k = 16 and distances 2, 4k - 1 and 4k = 64, the most amg_junction_paths takes, on a graph made from
+    reads: paths of 64 nodes that 63 cuts off"""
+    _search_prunes(AT_THE_LIMIT, 63)
+
+
+def _search_prunes(case, short):
+    g, _ = _graph(*case)
     assert g is not None
     v = g._v()
     k4 = g.get_kmerSize() * 4
     n_paths, exact = {}, False
-    for d in (2, 3, k4):
+    for d in (2, short, k4):
         found = g._engine.junction_paths(d)
         assert found["flags"] == 0
         v.ensure_hashes(np.unique(np.concatenate([found["path_node"], found["junction_node"]])).tolist())
@@ -94,12 +115,16 @@ def test_junction_search_prunes_at_every_distance():
         exact = exact or any(len(p) == d for x in want.values() for p in x)
     # not vacuous: a path that uses the whole distance, and a distance that cuts paths off
     assert exact
-    assert min(n_paths[2], n_paths[3]) < n_paths[k4]
+    assert min(n_paths[2], n_paths[short]) < n_paths[k4]
+    if case == AT_THE_LIMIT:   # paths of 4k nodes exactly, which 4k - 1 cuts off
+        assert any(len(p) == k4 for x in want.values() for p in x)
+        assert n_paths[2] < n_paths[short] < n_paths[k4]
 
 
-@pytest.mark.parametrize("case", CASES[:3])
+@pytest.mark.parametrize("case", CASES[:3] + LARGE_K)
 def test_sketch_sizes_and_overlaps(case):
     g, fq = _graph(*case)
+    assert g is not None or case not in LARGE_K
     if g is None:
         pytest.skip("palindromic gene-mer")
     starts = g.identify_potential_bubble_starts()
@@ -123,6 +148,7 @@ def test_sketch_sizes_and_overlaps(case):
                     assert dev.compare(high, low) == (len(a), len(b), len(a & b))
                     compared += 1
     assert compared > 0 or not starts
+    assert compared > 0 or case not in LARGE_K
 
 
 def test_sequences_in_another_order_than_the_reads():
@@ -142,8 +168,14 @@ def test_sequences_in_another_order_than_the_reads():
         assert one._size == two._size and one._common_of == two._common_of
 
 
-@pytest.mark.parametrize("case", CASES + [(91, 2000, 60, 800, 5, 0.02)])   # (the last one: hundreds of junctions)
+def _genes(reads):
+    return {r: list(v) for r, v in reads.items()}
+
+
+@pytest.mark.parametrize("case", CASES + [(91, 2000, 60, 800, 5, 0.02)] + LARGE_K)   # (the sixth: hundreds of junctions)
 def test_whole_step_equals_the_objects_way(case, monkeypatch):
+    changed = []
+
     def run(by_objects):
         if by_objects:
             monkeypatch.setenv("AMG_BUBBLES_BY_OBJECTS", "1")
@@ -152,7 +184,9 @@ def test_whole_step_equals_the_objects_way(case, monkeypatch):
         g, fq = _graph(*case)
         if g is None:
             return None
+        before = _genes(g.get_reads())
         reads, pos, covs, _ = g.correct_low_coverage_paths(fq, set(), 1, 2, set(), True)
+        changed.append(sum(1 for r, v in before.items() if list(reads[r]) != v))
         return ({r: list(v) for r, v in reads.items()}, {r: [tuple(p) for p in v] for r, v in pos.items()},
                 [float(c) for c in covs])
     a, b = run(False), run(True)
@@ -161,6 +195,44 @@ def test_whole_step_equals_the_objects_way(case, monkeypatch):
     assert a[2] == b[2]
     assert a[0] == b[0]
     assert a[1] == b[1]
+    if case in LARGE_K:   # two path coverages and a read rewritten, by the objects' way too
+        assert len(b[2]) >= 2 and changed[1] >= 1
+
+
+@pytest.mark.parametrize("case", LARGE_K)
+def test_the_device_takes_its_share_at_large_k(case):
+    """every device step of bubble popping may leave its work to the objects' way and say nothing (a distance beyond 64
+    levels, a call that does not fit, lists beyond the rewrite call's limits): at k = 7 ... 16 none of them does.  The
+    environment is left alone, so that a run under AMG_BUBBLES_BY_OBJECTS=1 fails here."""
+    g, fq = _graph(*case)
+    assert g is not None
+    k = g.get_kmerSize()
+    found = g._junction_paths_on_device()
+    assert found is not None
+    components, paths_of = found
+    with_bubble = longest = 0
+    for component in components:
+        if component not in paths_of:
+            continue
+        unique = list({tuple(sorted([p, [(h, -d) for h, d in reversed(p)]])[0]) for p in paths_of[component]})
+        longest = max([longest] + [len(p) for p in unique])
+        shortest_first = sorted(g.filter_paths_between_bubble_starts(unique), key=lambda e: len(e[0]))
+        bubbles = g.separate_paths_by_terminal_nodes(shortest_first)
+        if any(len(entries) > 1 for entries in bubbles.values()):
+            overlaps = g._path_overlaps_on_device(bubbles, fq)
+            assert overlaps is not None
+            assert overlaps._common_of and min(overlaps._size) > 0
+            with_bubble += 1
+    assert with_bubble >= 1
+    assert k < 15 or longest > 2 * k
+    before, genes_before = dict(g._engine.pop_rewrite_stats), _genes(g.get_reads())
+    reads, _, covs, _ = g.correct_low_coverage_paths(fq, set(), 1, 2, set(), True)
+    after = g._engine.pop_rewrite_stats
+    assert after["calls"] - before["calls"] >= 1
+    assert after["rewritten"] - before["rewritten"] >= 1
+    assert after["declined"] - before["declined"] == 0
+    assert len(covs) >= 2
+    assert sum(1 for r, v in genes_before.items() if list(reads[r]) != v) >= 1
 
 
 def test_raw_calls_on_a_graph_without_junctions():
